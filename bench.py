@@ -7,7 +7,7 @@ concurrent parameter-server jobs co-scheduled on the same GPUs, weak scaling
 (per-GPU batch work fixed as N grows).
 
 Launch (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   # N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
   #        --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -68,6 +68,19 @@ def parse_args():
                         "block migration of the last rank, then StartWorker"
                         " + migration back (BASELINE config #5); emits an "
                         "elastic_timeline field")
+    p.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                   help="direct mode: after the timed steps write what the "
+                        "last step produced (per job: the model table after "
+                        "the push and the trainer's step products) as "
+                        "DIR/<name>.npy, float32; large arrays keep a fixed "
+                        "seeded sample of rows. The clock warm-up then spins "
+                        "on scratch matmuls instead of extra job steps, so "
+                        "exactly warmup+steps steps precede the dump")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement. A plain run "
+                        "already does nothing but the headline (runtime/"
+                        "elastic/per-app figures are explicit --mode/--apps "
+                        "runs), so today this adds nothing")
     return p.parse_args()
 
 
@@ -155,6 +168,63 @@ class JobBench:
             with self.tus.net(self.job.job_id, self._next_phase()):
                 self.trainer.push_update()
             self.examples_per_batch = self.trainer.num_batch_examples()
+
+    def outputs(self):
+        """What the last step() left for its caller: the model table after
+        the push, plus the trainer's products of that step. pull_all is a
+        collective at world > 1 — every rank must call this."""
+        tr = self.trainer
+        app = self.job.app
+        out = {f"{app}_model": next(iter(self.tables.values())).pull_all()}
+        if app == "nmf":
+            out["nmf_L"] = tr.L
+            out["nmf_rgrad"] = tr.rgrad
+        elif app == "mlr":
+            out["mlr_grad"] = tr.grad_raw
+        elif app == "lda":
+            # alias_wave updates a doc's counts through LDS atomics in
+            # hardware order: nothing guarantees these bit-identical from
+            # run to run (on MI355X two runs did match exactly)
+            out["lda_assignments"] = tr._new_z
+            out["lda_doc_topic"] = tr.doc_topic
+        return out
+
+
+# --dump-outputs: per-array cap; 8 arrays at most -> 48 MiB, under the
+# 64 MB the whole dump may take
+DUMP_ARRAY_BYTES = 6 << 20
+
+
+def dump_outputs(out_dir: str, arrays) -> None:
+    """Write name -> tensor as float32 (float64 stays) .npy files; an array
+    over the cap keeps a fixed, seeded sample of its rows."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    assert len(arrays) * DUMP_ARRAY_BYTES < 64e6, sorted(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        width = 8 if t.dtype == torch.float64 else 4
+        n = t.shape[0] if t.dim() else 1
+        keep = DUMP_ARRAY_BYTES // max(1, width * t.numel() // max(1, n))
+        if t.dim() and keep < n:
+            idx = np.sort(np.random.default_rng(0).choice(
+                n, size=max(1, keep), replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.to(device="cpu", dtype=dt).contiguous().numpy())
+
+
+def spin_gpu(seconds: float, device) -> None:
+    """Hold the GPU under load with scratch matmuls: ramps the clocks like
+    extra warmup rounds do, without advancing any job's state."""
+    a = torch.ones((4096, 4096), device=device)
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(8):
+            a @ a
+        torch.cuda.synchronize()
 
 
 def run_runtime_mode(args, ctx, cp, jobs):
@@ -379,7 +449,12 @@ def main():
     # first K steps at low clocks. Timed region is untouched (full work).
     warm_min_s = float(os.environ.get("HARMONY_BENCH_MIN_WARMUP_S", "2.0"))
     run_steps(args.warmup)
-    if dev_cuda and args.warmup > 0:
+    if dev_cuda and args.warmup > 0 and args.dump_outputs:
+        # dumped arrays must come from the same step count in every run:
+        # ramp the clocks without stepping the jobs
+        sync_all()
+        spin_gpu(warm_min_s, ctx.device)
+    elif dev_cuda and args.warmup > 0:
         sync_all()
         tw = time.perf_counter()
         while True:
@@ -411,6 +486,12 @@ def main():
     examples_per_step_rank = sum(b.examples_per_batch for b in benches)
     total_examples = examples_per_step_rank * args.steps * world
     value = total_examples / elapsed
+    if args.dump_outputs:
+        arrays = {}
+        for b in benches:           # job order: same collectives everywhere
+            arrays.update(b.outputs())
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         out = {
             "metric": "aggregate_examples_per_sec_3job",

@@ -566,10 +566,41 @@ def _async_migrate_job_worker(rank, world):
     from harmony_amd.runtime.bootstrap import init_executor
 
     ctx = init_executor(RuntimeConfig(device="cuda", backend="gloo"))
+    # One batch's worth of work before the job: an MLR compute phase of
+    # the job's shapes, and a pull + push on a throwaway one-sided table.
+    # A process's first batch pays the first use of the GEMM and one-sided
+    # kernels (measured: 0.8 s, against 0.7 ms for every later batch), and
+    # the async plane does not couple the ranks: the two first batches
+    # differed by 15 ms, more than the other 11 batches take together, and
+    # when rank 0 was the quick one it finished the job before its peer
+    # had reported one metric window, so no plan was ever decided. With
+    # that paid here the first batch costs what the others do.
+    from harmony_amd import ops
+    from harmony_amd.config import TableConfig
+    from harmony_amd.et.onesided import OneSidedTable
+
+    C, F, B, P = 4, 32, 512, 4
+    x = torch.randn(B, F, device=ctx.device)
+    W = torch.randn(C, F, device=ctx.device)
+    p, _, _ = ops.mlr_forward(x, W, torch.zeros(B, dtype=torch.int64,
+                                                device=ctx.device))
+    _ = ops.mlr_grad_gemm(p, x) / B + 1e-4 * W
+    wt = OneSidedTable(
+        TableConfig(table_id="os_warm", num_keys=C * P, value_dim=F // P,
+                    num_blocks=C * P, update_fn="add", init_fn="zeros"),
+        rank, world, ctx.device, store=ctx.store)
+    _barrier(ctx.store, "w_alloc", rank, world)
+    wt.connect()
+    _barrier(ctx.store, "w_conn", rank, world)
+    wt.push(torch.arange(C * P, device=ctx.device), wt.pull_full()[:C * P])
+    wt.fence()
+    torch.cuda.synchronize()
+    _barrier(ctx.store, "w_done", rank, world)
+    wt.close()
     job = JobConfig(job_id="os_mlr_mig", app="mlr", max_num_epochs=6,
                     num_mini_batches=2, optimizer_period=2,
-                    app_args={"num_classes": 4, "num_features": 32,
-                              "num_parts_per_class": 4, "batch_size": 512,
+                    app_args={"num_classes": C, "num_features": F,
+                              "num_parts_per_class": P, "batch_size": B,
                               "step_size": 0.3, "one_sided": True})
     opt = SampleOptimizers.rotate_blocks("os_mlr_mig/mlr_model", stride=2)
     m = run_job(job, ctx, optimizer=opt)
