@@ -3,4 +3,4 @@
 # ETDolphinLauncher mode). Multi-GPU: wrap with torchrun (see
 # harmony_amd/standalone.py).
 cd "$(dirname "$0")/.."
-exec python -m harmony_amd.standalone -app shortest_path "$@"
+exec python -m harmony_amd.standalone -app shortestpath "$@"

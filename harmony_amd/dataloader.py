@@ -14,6 +14,8 @@ Parsers accept the reference's sample file formats
   lda:   "word word word ..."            (one doc per line)
   lasso: "label featIdx:val ..."
   gbt:   "label featIdx:val ..." + .meta "featIdx:type ..."
+  pagerank:     "src dst dst ..."        (adjacency list, inputs/adj_list)
+  shortestpath: "src dst w dst w ..."    (weighted, inputs/shortest_path)
 Comment lines (#) and blank lines are skipped.
 """
 
@@ -187,6 +189,89 @@ def parse_lda_split(path: str, rank: int, world_size: int):
         buf = _read_split_bytes(path, split)
         return tuple(nat.parse_lda_bytes(buf))
     return parse_lda(read_split(path, split))
+
+
+# ------------------------------------------------------ Pregel graph input
+
+def parse_graph(lines, weighted: bool):
+    """Adjacency-list lines -> (src int64 [E], dst int64 [E],
+    w float32 [E] or None, max_id).
+
+    unweighted (pagerank):     "src dst dst dst ..."
+    weighted (shortestpath):   "src dst w dst w ..."   integer weights
+    (reference NoneEdgeValueGraphParser / DefaultGraphParser). A line with
+    only "src" is a vertex with no out-edges; a trailing unpaired token of a
+    weighted line is ignored, as upstream does; '#' lines and empty lines
+    are skipped. max_id is the largest id seen as a source or destination
+    (-1 for empty input). Weights are stored as float32, which is exact for
+    integers up to 2^24."""
+    src: List[int] = []
+    dst: List[int] = []
+    ws: List[float] = []
+    max_id = -1
+    for ln in lines:
+        ln = ln.strip()
+        if not ln or ln.startswith("#"):
+            continue
+        toks = ln.split()
+        s = int(toks[0])
+        max_id = max(max_id, s)
+        if weighted:
+            for i in range(1, len(toks) - 1, 2):
+                src.append(s)
+                dst.append(int(toks[i]))
+                ws.append(float(int(toks[i + 1])))
+        else:
+            for tok in toks[1:]:
+                src.append(s)
+                dst.append(int(tok))
+    if dst:
+        max_id = max(max_id, max(dst))
+    return (torch.tensor(src, dtype=torch.int64),
+            torch.tensor(dst, dtype=torch.int64),
+            torch.tensor(ws, dtype=torch.float32) if weighted else None,
+            max_id)
+
+
+def parse_graph_file(path: str, weighted: bool, world_size: int = 1):
+    """Parse a whole adjacency-list file (native byte scanner when the
+    extension is built, else the Python parser; same result either way)."""
+    path = _strip_scheme(path)
+    nat = _native(world_size)
+    if nat is not None:
+        with open(path, "rb") as f:
+            src, dst, w, mx = nat.parse_graph_bytes(f.read(), bool(weighted))
+        return src, dst, (w if weighted else None), int(mx[0])
+    size = os.path.getsize(path)
+    return parse_graph(read_split(path, (0, size)), weighted)
+
+
+def graph_num_vertices(path: str, weighted: bool, world_size: int = 1) -> int:
+    """max id over sources and destinations + 1 — identical on every rank,
+    and known before any table exists."""
+    return parse_graph_file(path, weighted, world_size)[3] + 1
+
+
+def load_graph_partition(path: str, lo: int, hi: int, weighted: bool,
+                         world_size: int = 1, parsed=None):
+    """This rank's part of an adjacency-list file: every rank scans the
+    WHOLE file and keeps the edges whose source lies in [lo, hi) — no
+    communication (same idea as load_keyless_split, which also scans all
+    splits). Returns (row_ptr int64 [hi-lo+1], edge_dst int64 [E_local],
+    edge_w float32 [E_local] or None, num_vertices, num_edges_global); the
+    local CSR keeps each vertex's edges in file order. `parsed` reuses the
+    result of an earlier parse_graph_file of the same file (the scan that
+    sized the tables) instead of reading it again."""
+    src, dst, w, max_id = parsed or parse_graph_file(path, weighted,
+                                                     world_size)
+    keep = (src >= lo) & (src < hi)
+    src, dst = src[keep] - lo, dst[keep]
+    order = torch.argsort(src, stable=True)
+    n_local = max(0, hi - lo)
+    row_ptr = torch.zeros(n_local + 1, dtype=torch.int64)
+    row_ptr[1:] = torch.cumsum(torch.bincount(src, minlength=n_local), 0)
+    edge_w = w[keep][order] if w is not None else None
+    return row_ptr, dst[order], edge_w, max_id + 1, int(keep.shape[0])
 
 
 def load_keyless_split(path: str, rank: int, world_size: int,

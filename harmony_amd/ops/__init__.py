@@ -15,6 +15,7 @@ Kernel inventory (reference hot loops):
   K7  lda_gibbs           SparseLDASampler.java:141-274
   K9  scatter-apply       LDAETModelUpdateFunction.java:43-64
   K12 loss reductions     NMFTrainer.java:414-456 etc.
+  K13 pregel_pull         pregel MessageManager.addMessage + MessageCombiner
 """
 
 from __future__ import annotations
@@ -643,6 +644,80 @@ def dense_apply(shard: torch.Tensor, delta: torch.Tensor,
     assert _use_hip(shard), "dense_apply is the GPU fused path"
     _hip.dense_apply(shard, delta.contiguous(), _APPLY_MODES[update_fn_name],
                      float(step_size), float(max_val))
+
+
+# ---------------------------------------------------------------------------
+# K13: Pregel pull (send + combine over a static inverted edge index)
+# ---------------------------------------------------------------------------
+
+_PULL_COMBINERS = {"add": 0, "min": 1}
+
+
+def pregel_pull_group(num_rows: int, num_in_edges: int) -> int:
+    """Lanes that cooperate on one row in the K13 kernel: the smallest power
+    of two >= the graph's mean in-degree, clamped to 1..64. A function of
+    the graph alone, so a graph always runs with the same summation order."""
+    mean = num_in_edges / max(1, num_rows)
+    g = 1
+    while g < 64 and g < mean:
+        g *= 2
+    return g
+
+
+def pregel_pull(in_ptr: torch.Tensor, in_src: torch.Tensor,
+                in_w: Optional[torch.Tensor], w_const: float,
+                vert_msg: torch.Tensor, send_mask: Optional[torch.Tensor],
+                combiner: str, add_weight: bool, _force_group: int = 0
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One superstep's message send + combine as a gather-reduce (K13,
+    ops/csrc/pregel.hip; replaces reference MessageManager.addMessage with a
+    MessageCombiner). The pull index lists, for each of R destination rows,
+    its sources: in_ptr int64 [R+1], in_src int32 [Ein] (local source
+    index), in_w float32 [Ein] or None.
+
+    out[r] combines, over the in-edges e of row r whose source is sending,
+    vert_msg[src] (+ in_w[e], or w_const when in_w is None, if add_weight);
+    the combiner's identity (0 for add, +inf for min) when nothing is sent.
+    flag[r] = 1 iff at least one in-edge's source was sending. send_mask
+    (uint8/bool [n_local]) None means every source sends.
+    Returns (out float32 [R], flag uint8 [R]).
+
+    CPU tensors (and HARMONY_FORCE_TORCH_OPS=1) take the torch reference
+    below, which is also the kernel's test oracle. _force_group is for tests:
+    it overrides the lanes-per-row choice of pregel_pull_group."""
+    mode = _PULL_COMBINERS[combiner]
+    R = in_ptr.shape[0] - 1
+    if _use_hip(vert_msg):
+        group = _force_group or pregel_pull_group(R, in_src.shape[0])
+        mask = None
+        if send_mask is not None:
+            mask = (send_mask.view(torch.uint8)
+                    if send_mask.dtype == torch.bool
+                    else send_mask.to(torch.uint8)).contiguous()
+        out, flag = _hip.pregel_pull(
+            in_ptr.contiguous(), in_src.contiguous(),
+            None if in_w is None else in_w.contiguous(), float(w_const),
+            vert_msg.contiguous(), mask, mode, bool(add_weight), int(group))
+        return out, flag
+    dev = vert_msg.device
+    counts = in_ptr[1:] - in_ptr[:-1]
+    row = torch.repeat_interleave(torch.arange(R, device=dev), counts)
+    src = in_src.long()
+    v = vert_msg[src]
+    if add_weight:
+        v = v + (in_w if in_w is not None else w_const)
+    if send_mask is not None:
+        sending = send_mask[src].bool()
+        row, v = row[sending], v[sending]
+    flag = torch.zeros(R, dtype=torch.uint8, device=dev)
+    flag[row] = 1
+    if mode == 1:
+        out = torch.full((R,), float("inf"), dtype=vert_msg.dtype, device=dev)
+        out.scatter_reduce_(0, row, v, reduce="amin", include_self=True)
+    else:
+        out = torch.zeros(R, dtype=vert_msg.dtype, device=dev)
+        out.index_add_(0, row, v)
+    return out, flag
 
 
 # ---------------------------------------------------------------------------

@@ -88,6 +88,13 @@ std::vector<torch::Tensor> parse_nmf_bytes(const std::string& buf);
 std::vector<torch::Tensor> parse_libsvm_bytes(const std::string& buf,
                                               int64_t num_features);
 std::vector<torch::Tensor> parse_lda_bytes(const std::string& buf);
+std::vector<torch::Tensor> parse_graph_bytes(const std::string& buf,
+                                             bool weighted);
+std::vector<torch::Tensor> pregel_pull(
+    torch::Tensor in_ptr, torch::Tensor in_src,
+    c10::optional<torch::Tensor> in_w, double w_const, torch::Tensor vert_msg,
+    c10::optional<torch::Tensor> send_mask, int64_t combiner, bool add_weight,
+    int64_t group);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlr_softmax_grad", &mlr_softmax_grad,
@@ -138,4 +145,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("parse_libsvm_bytes", &parse_libsvm_bytes,
         "native libsvm-style parser (mlr/gbt/lasso)");
   m.def("parse_lda_bytes", &parse_lda_bytes, "native LDA doc parser");
+  m.def("parse_graph_bytes", &parse_graph_bytes,
+        "native adjacency-list parser (pagerank / shortestpath)");
+  m.def("pregel_pull", &pregel_pull,
+        "Pregel send+combine as a CSR gather-reduce over the pull index "
+        "(K13)");
 }

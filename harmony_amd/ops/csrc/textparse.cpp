@@ -223,3 +223,68 @@ std::vector<torch::Tensor> parse_lda_bytes(const std::string& buf) {
   }
   return {off, wo};
 }
+
+// Pregel adjacency lists (reference DefaultGraphParser.java:44 and
+// NoneEdgeValueGraphParser.java:48): unweighted "src dst dst ..." or
+// weighted "src dst w dst w ..." with integer weights (a trailing unpaired
+// token is ignored, as upstream does). A line holding only "src" is a
+// vertex without out-edges: it emits no edge but still counts towards
+// max_id. -> (src [E], dst [E], w float32 [E] (empty if unweighted),
+// max_id [1], -1 when the input names no vertex)
+std::vector<torch::Tensor> parse_graph_bytes(const std::string& buf,
+                                             bool weighted) {
+  const int T = nthreads();
+  auto chunks = line_chunks(buf.data(), (int64_t)buf.size(), T);
+  std::vector<std::vector<int64_t>> srcs(T), dsts(T);
+  std::vector<std::vector<float>> ws(T);
+  std::vector<int64_t> maxid(T, -1);
+  std::vector<std::thread> ths;
+  for (int t = 0; t < T; ++t) {
+    ths.emplace_back([&, t] {
+      Cursor c{chunks[t].first, chunks[t].second};
+      int64_t mx = -1;
+      while (!c.done()) {
+        if (c.at_comment_or_empty()) { c.next_line(); continue; }
+        const int64_t s = c.read_long();
+        mx = std::max(mx, s);
+        while (!c.eol()) {
+          const int64_t d = c.read_long();
+          float w = 0.f;
+          if (weighted) {
+            if (c.eol()) break;            // unpaired trailing token
+            w = (float)c.read_long();
+          }
+          srcs[t].push_back(s);
+          dsts[t].push_back(d);
+          if (weighted) ws[t].push_back(w);
+          mx = std::max(mx, d);
+        }
+        c.next_line();
+      }
+      maxid[t] = mx;
+    });
+  }
+  for (auto& th : ths) th.join();
+  int64_t total = 0, mx = -1;
+  for (int t = 0; t < T; ++t) {
+    total += (int64_t)srcs[t].size();
+    mx = std::max(mx, maxid[t]);
+  }
+  auto so = torch::empty({total}, torch::kInt64);
+  auto dn = torch::empty({total}, torch::kInt64);
+  auto wo = torch::empty({weighted ? total : 0}, torch::kFloat32);
+  int64_t off = 0;
+  for (int t = 0; t < T; ++t) {
+    int64_t n = (int64_t)srcs[t].size();
+    if (n) {
+      std::memcpy(so.data_ptr<int64_t>() + off, srcs[t].data(), n * 8);
+      std::memcpy(dn.data_ptr<int64_t>() + off, dsts[t].data(), n * 8);
+      if (weighted)
+        std::memcpy(wo.data_ptr<float>() + off, ws[t].data(), n * 4);
+    }
+    off += n;
+  }
+  auto mo = torch::empty({1}, torch::kInt64);
+  mo.data_ptr<int64_t>()[0] = mx;
+  return {so, dn, wo, mo};
+}

@@ -53,6 +53,28 @@ class Computation:
         each outgoing edge of the local CSR (dst = graph.edge_dst)."""
         raise NotImplementedError
 
+    # Optional per-VERTEX form of compute() for the fused engine path
+    # (PregelEngine(fused=True)): every out-edge of a vertex carries the
+    # same value, so the engine needs one message per vertex and fans it
+    # out through the pull index instead of a [num_local_edges] tensor.
+    # edge_op says what an edge does to it: "copy" (message as is) or
+    # "add_weight" (message + the edge's weight).
+    edge_op = "copy"
+
+    def vertex_messages(self, superstep: int, values: torch.Tensor,
+                        incoming: torch.Tensor, has_msg: torch.Tensor, graph
+                        ) -> Tuple[torch.Tensor, Optional[torch.Tensor],
+                                   Optional[torch.Tensor], torch.Tensor]:
+        """Returns (new_values, vert_msg or None, send_mask or None,
+        active_mask). vert_msg: [n_local] float32, the value each vertex
+        sends along all its out-edges (None: nobody sends); send_mask:
+        [n_local] bool, the vertices that send (None: all of them)."""
+        raise NotImplementedError
+
+    def has_vertex_messages(self) -> bool:
+        return (type(self).vertex_messages
+                is not Computation.vertex_messages)
+
 
 @dataclass
 class LocalGraph:
@@ -63,14 +85,86 @@ class LocalGraph:
     edge_dst: torch.Tensor         # [n_local_edges] global dst ids
     out_degree: torch.Tensor       # [n_local]
     num_vertices_global: int
+    # per-edge values (reference Vertex<V,E> / DefaultEdge), aligned with
+    # edge_dst; None for graphs without edge values
+    edge_weight: Optional[torch.Tensor] = None   # [n_local_edges] float32
+
+
+@dataclass
+class PullIndex:
+    """The local edge list inverted once: for each destination row, the
+    local sources that send to it (see build_pull_index)."""
+
+    n_local: int
+    in_ptr: torch.Tensor           # int64 [R+1], R = n_local + U
+    in_src: torch.Tensor           # int32 [Ein] local source vertex index
+    in_w: Optional[torch.Tensor]   # float32 [Ein] or None
+    remote_keys: torch.Tensor      # int64 [U] global ids of rows >= n_local
+
+
+def build_pull_index(graph: LocalGraph, msg_table: Table) -> PullIndex:
+    """Invert the local CSR into a pull index for ops.pregel_pull.
+
+    Rows 0..n_local-1 are the local vertices in shard order (a vertex
+    without in-edges keeps an empty range); rows n_local..n_local+U-1 are
+    the U distinct destinations of local edges that another rank owns, in
+    ascending key order (`remote_keys`). A stable sort keeps every row's
+    sources in original edge order, which fixes the summation order.
+
+    The index is tied to `msg_table`'s ownership at the time of the call:
+    which destinations are local rows and which are remote is baked in.
+    Pregel tables do not migrate mid-run, so it is built once per job in
+    PregelEngine.set_graph."""
+    dev = graph.edge_dst.device
+    n_local = int(graph.row_ptr.shape[0]) - 1
+    n_edges = int(graph.edge_dst.shape[0])
+    if n_local >= 2 ** 31 or n_edges >= 2 ** 31:
+        raise ValueError(
+            f"pull index needs n_local ({n_local}) and the local edge count "
+            f"({n_edges}) below 2^31: in_src and the kernel's source index "
+            "are int32")
+    dst = graph.edge_dst.to(torch.int64)
+    counts = graph.row_ptr[1:] - graph.row_ptr[:-1]
+    src_local = torch.repeat_interleave(
+        torch.arange(n_local, dtype=torch.int64, device=dev), counts)
+    owner = msg_table.ownership.owner.to(dev)[msg_table.part.block_of(dst)]
+    is_local = owner == msg_table.rank
+    row_of_edge = torch.empty(n_edges, dtype=torch.int64, device=dev)
+    local_rows = msg_table.local_rows_of(dst[is_local])
+    if local_rows.numel() and int(local_rows.max()) >= n_local:
+        raise ValueError("a locally owned destination lies outside the "
+                         "local vertex range the graph was built for")
+    row_of_edge[is_local] = local_rows
+    remote_keys, inv = torch.unique(dst[~is_local], return_inverse=True)
+    row_of_edge[~is_local] = n_local + inv
+    num_rows = n_local + int(remote_keys.shape[0])
+    order = torch.argsort(row_of_edge, stable=True)
+    in_ptr = torch.zeros(num_rows + 1, dtype=torch.int64, device=dev)
+    in_ptr[1:] = torch.cumsum(
+        torch.bincount(row_of_edge, minlength=num_rows), 0)
+    in_w = None
+    if graph.edge_weight is not None:
+        in_w = graph.edge_weight.to(torch.float32)[order].contiguous()
+    return PullIndex(n_local=n_local, in_ptr=in_ptr,
+                     in_src=src_local[order].to(torch.int32).contiguous(),
+                     in_w=in_w, remote_keys=remote_keys)
 
 
 class PregelEngine:
     def __init__(self, job: JobConfig, comp: Computation, num_vertices: int,
                  ctx, cp: ControlPlane, tus: Optional[TaskUnitScheduler] = None,
-                 max_supersteps: int = 100):
+                 max_supersteps: int = 100, fused: bool = False):
         self.job = job
         self.comp = comp
+        # fused: send + combine through the pull index (ops.pregel_pull,
+        # K13) instead of per-edge messages + a combining scatter
+        self.fused = bool(fused)
+        if self.fused and (comp.msg_dim != 1
+                           or not comp.has_vertex_messages()):
+            raise ValueError(
+                "fused=True needs msg_dim == 1 and a Computation that "
+                "implements vertex_messages()")
+        self.pull: Optional[PullIndex] = None
         self.graph: Optional[LocalGraph] = None   # set_graph() after tables
         self.ctx = ctx
         self.cp = cp
@@ -109,6 +203,10 @@ class PregelEngine:
 
     def set_graph(self, graph: LocalGraph) -> None:
         self.graph = graph
+        if self.fused:
+            # both message tables share one layout; see build_pull_index
+            # for why the index is valid for the whole run
+            self.pull = build_pull_index(graph, self.msg[0])
 
     def _next_phase(self):
         self._phase += 1
@@ -122,6 +220,8 @@ class PregelEngine:
 
     def run(self) -> torch.Tensor:
         """Run supersteps to halt; returns final local vertex values."""
+        if self.fused:
+            return self._run_fused()
         comp, g = self.comp, self.graph
         dev = self.ctx.device
         n_local = g.row_ptr.shape[0] - 1
@@ -163,6 +263,70 @@ class PregelEngine:
             # incremental has-message mask from the owner-apply's touched
             # keys (replaces the full-shard != identity scan)
             has_msg = torch.zeros(n_local, dtype=torch.bool, device=dev)
+            touched = getattr(self.msg[self.cur], "last_touched_keys", None)
+            if touched is not None and touched.numel():
+                rows = self.msg[self.cur].local_rows_of(touched.to(dev))
+                has_msg[rows[rows < n_local]] = True
+            if sums is not None and int(sums[0]) == 0 and int(sums[1]) == 0:
+                break
+        self.vertex_table.shard[:n_local] = values
+        return values
+
+    def _run_fused(self) -> torch.Tensor:
+        """run() with send + combine as ONE gather-reduce per superstep
+        (K13): no per-edge message tensor, no per-superstep sort. Local
+        destinations are written straight into the next message shard;
+        only the combined values of remote destinations go through the
+        push, which every rank still enters once per superstep."""
+        from harmony_amd import ops
+
+        comp, g, pull = self.comp, self.graph, self.pull
+        dev = self.ctx.device
+        n_local = pull.n_local
+        n_remote = int(pull.remote_keys.shape[0])
+        values = self.vertex_table.shard[:n_local]
+        ident = comp.msg_identity
+        for t in self.msg:
+            self._clear(t, ident)
+        has_msg = torch.zeros(n_local, dtype=torch.bool, device=dev)
+        jid = self.job.job_id
+        zero_keys = torch.empty(0, dtype=torch.int64, device=dev)
+        zero_msgs = torch.empty((0, 1), dtype=torch.float32, device=dev)
+        add_weight = comp.edge_op == "add_weight"
+        w_const = float(getattr(comp, "edge_weight", 0.0))
+        for step in range(self.max_supersteps):
+            self.supersteps_run = step + 1
+            incoming = self.msg[self.cur].shard[:n_local]
+            values, vert_msg, send_mask, active = comp.vertex_messages(
+                step, values, incoming, has_msg, g)
+            self._clear(self.msg[self.cur], ident)
+            nxt = self.msg[1 - self.cur]
+            nxt.last_touched_keys = None
+            keys, msgs = zero_keys, zero_msgs
+            has_msg = torch.zeros(n_local, dtype=torch.bool, device=dev)
+            n_active = active.sum()
+            if vert_msg is None:
+                vote = torch.stack([n_active, torch.zeros_like(n_active)])
+            else:
+                out, flag = ops.pregel_pull(
+                    pull.in_ptr, pull.in_src, pull.in_w, w_const,
+                    vert_msg.to(torch.float32), send_mask, comp.combiner,
+                    add_weight)
+                # local rows first: unflagged rows hold the identity, like
+                # the cleared shard, and the push below combines remote
+                # ranks' contributions on top of them
+                nxt.shard[:n_local, 0] = out[:n_local]
+                has_msg = flag[:n_local].bool()
+                if n_remote:
+                    sel = flag[n_local:].bool()
+                    keys = pull.remote_keys[sel]
+                    msgs = out[n_local:][sel].unsqueeze(1)
+                vote = torch.stack([n_active, flag.sum()])
+            vote = vote.to("cpu", torch.int64)
+            with self.tus.net(jid, self._next_phase()):
+                sums = nxt.update(keys, msgs, assume_unique=True,
+                                  piggyback=vote)
+            self.cur = 1 - self.cur
             touched = getattr(self.msg[self.cur], "last_touched_keys", None)
             if touched is not None and touched.numel():
                 rows = self.msg[self.cur].local_rows_of(touched.to(dev))

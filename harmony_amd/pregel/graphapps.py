@@ -19,6 +19,7 @@ class PageRankComputation(Computation):
     combiner = "add"
     msg_identity = 0.0
     msg_dim = 1
+    edge_op = "copy"
 
     def __init__(self, num_iters: int = 20):
         self.num_iters = num_iters
@@ -40,6 +41,24 @@ class PageRankComputation(Computation):
                             device=values.device)
         return new, edge_msgs, active
 
+    def vertex_messages(self, superstep, values, incoming, has_msg,
+                        graph: LocalGraph):
+        """compute() with one message per vertex (every out-edge carries
+        val/out_deg) — same arithmetic, no per-edge expansion."""
+        n = graph.num_vertices_global
+        if superstep == 0:
+            new = torch.full_like(values, 1.0 / n)
+        else:
+            new = 0.15 / n + 0.85 * incoming
+        if superstep >= self.num_iters:
+            active = torch.zeros(values.shape[0], dtype=torch.bool,
+                                 device=values.device)
+            return new, None, None, active
+        vert_msg = new.squeeze(1) / graph.out_degree.clamp_min(1)
+        active = torch.ones(values.shape[0], dtype=torch.bool,
+                            device=values.device)
+        return new, vert_msg, None, active
+
 
 class ShortestPathComputation(Computation):
     """Min-combiner relaxation: a vertex adopts the smallest incoming
@@ -49,12 +68,14 @@ class ShortestPathComputation(Computation):
     combiner = "min"
     msg_identity = float("inf")
     msg_dim = 1
+    edge_op = "add_weight"
 
     def __init__(self, source: int = 0, edge_weight: float = 1.0):
         self.source = source
         self.edge_weight = edge_weight
 
-    def compute(self, superstep, values, incoming, has_msg, graph: LocalGraph):
+    def _relax(self, superstep, values, incoming, has_msg, graph):
+        """-> (new distances, mask of the vertices that improved)."""
         dev = values.device
         n_local = values.shape[0]
         if superstep == 0:
@@ -70,17 +91,38 @@ class ShortestPathComputation(Computation):
                                torch.full_like(incoming, float("inf")))
             new = torch.minimum(values, cand)
             changed = (new < values).any(dim=1)
+        return new, changed
+
+    def compute(self, superstep, values, incoming, has_msg, graph: LocalGraph):
+        dev = values.device
+        n_local = values.shape[0]
+        new, changed = self._relax(superstep, values, incoming, has_msg,
+                                   graph)
         edge_msgs = None
         if bool(changed.any()):
             counts = graph.row_ptr[1:] - graph.row_ptr[:-1]
             per_edge_changed = changed.repeat_interleave(counts)
             dist_per_edge = new.squeeze(1).repeat_interleave(counts)
+            # each edge's own value (reference Vertex<V,E>) when the graph
+            # carries them, else the constant
+            w = (graph.edge_weight if graph.edge_weight is not None
+                 else self.edge_weight)
             msgs = torch.where(per_edge_changed,
-                               dist_per_edge + self.edge_weight,
+                               dist_per_edge + w,
                                torch.full_like(dist_per_edge, float("inf")))
             edge_msgs = msgs.unsqueeze(1)
         active = torch.zeros(n_local, dtype=torch.bool, device=dev)
         return new, edge_msgs, active
+
+    def vertex_messages(self, superstep, values, incoming, has_msg,
+                        graph: LocalGraph):
+        """compute() with one message per vertex: an improved vertex sends
+        its distance, and each edge adds its own weight on the way."""
+        new, changed = self._relax(superstep, values, incoming, has_msg,
+                                   graph)
+        active = torch.zeros(values.shape[0], dtype=torch.bool,
+                             device=values.device)
+        return new, new.squeeze(1), changed, active
 
 
 def make_ring_plus_random_graph(num_vertices: int, out_degree: int,
@@ -110,3 +152,18 @@ def make_ring_plus_random_graph(num_vertices: int, out_degree: int,
     return LocalGraph(vertex_lo=vertex_lo, row_ptr=row_ptr,
                       edge_dst=edge_dst.to(device), out_degree=out_deg,
                       num_vertices_global=num_vertices)
+
+
+def make_graph_from_edges(row_ptr: torch.Tensor, edge_dst: torch.Tensor,
+                          edge_weight, vertex_lo: int, num_vertices: int,
+                          device) -> LocalGraph:
+    """LocalGraph over a loaded partition (dataloader.load_graph_partition):
+    row_ptr/edge_dst are the local CSR of vertices [vertex_lo, vertex_lo +
+    n_local); edge_weight is the per-edge value tensor or None."""
+    row_ptr = row_ptr.to(device)
+    out_deg = (row_ptr[1:] - row_ptr[:-1]).to(torch.float32)
+    return LocalGraph(
+        vertex_lo=vertex_lo, row_ptr=row_ptr, edge_dst=edge_dst.to(device),
+        out_degree=out_deg, num_vertices_global=num_vertices,
+        edge_weight=(None if edge_weight is None
+                     else edge_weight.to(device, torch.float32)))

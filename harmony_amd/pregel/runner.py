@@ -3,13 +3,16 @@ PregelJobEntity + PregelMaster.start)."""
 
 from __future__ import annotations
 
+import os
 import time
 from typing import Optional
 
+from harmony_amd import dataloader as dl
 from harmony_amd.config import JobConfig
 from harmony_amd.pregel.engine import PregelEngine
 from harmony_amd.pregel.graphapps import (PageRankComputation,
                                           ShortestPathComputation,
+                                          make_graph_from_edges,
                                           make_ring_plus_random_graph)
 from harmony_amd.runtime.control import ControlPlane, TaskUnitScheduler
 from harmony_amd.utils import stable_seed
@@ -23,13 +26,56 @@ def local_vertex_range(num_vertices: int, rank: int, world: int):
     return lo, hi
 
 
+def _use_fused(setting, device) -> bool:
+    """-fused_messages auto|true|false; auto = on when the device is a GPU
+    and the HIP extension is loaded."""
+    from harmony_amd import ops
+
+    s = str(setting).lower()
+    if s in ("true", "1", "yes"):
+        return True
+    if s in ("false", "0", "no"):
+        return False
+    if s != "auto":
+        raise ValueError(f"-fused_messages must be auto|true|false, "
+                         f"got {setting!r}")
+    return device.type == "cuda" and ops.hip_available()
+
+
+def _write_part(out_dir: str, rank: int, lo: int, values) -> None:
+    """<dir>/part-<rank>: one "vertexId value" line per local vertex."""
+    out_dir = dl._strip_scheme(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    vals = values.reshape(-1).tolist()
+    with open(os.path.join(out_dir, f"part-{rank}"), "w") as f:
+        for i, v in enumerate(vals):
+            f.write(f"{lo + i} {v!r}\n")
+
+
 def run_pregel_job(job: JobConfig, ctx, cp: Optional[ControlPlane] = None,
                    tus: Optional[TaskUnitScheduler] = None) -> dict:
+    """App args: -input <adjacency list> (file:// accepted; without it the
+    synthetic ring+random graph of -num_vertices/-out_degree is used),
+    -output <dir> (each rank writes part-<rank>), -fused_messages
+    auto|true|false, plus -num_iters (pagerank) and -source/-edge_weight
+    (shortestpath)."""
     a = dict(num_vertices=1024, out_degree=4, num_iters=20, source=0,
-             edge_weight=1.0)
+             edge_weight=1.0, fused_messages="auto")
     a.update(job.app_args)
     cp = cp or ControlPlane(ctx.store, ctx.rank, ctx.world_size)
     n = int(a["num_vertices"])
+    weighted = job.app == "shortestpath"
+    parsed = None
+    if a.get("input"):
+        # first scan: the id range sizes the tables, so it comes before them
+        parsed = dl.parse_graph_file(a["input"], weighted, ctx.world_size)
+        n_file = parsed[3] + 1
+        if "num_vertices" not in job.app_args:
+            n = n_file
+        elif n < n_file:
+            raise ValueError(
+                f"-num_vertices {n} is smaller than the input's largest "
+                f"vertex id + 1 ({n_file})")
     # align the vertex partition with the table partition: the engine's
     # tables use contiguous even blocks, so the local range is rank-even too
     if job.app == "pagerank":
@@ -43,18 +89,32 @@ def run_pregel_job(job: JobConfig, ctx, cp: Optional[ControlPlane] = None,
     # the engine derives its shard layout from Table ownership; build tables
     # first, then the graph over the local key range
     engine = PregelEngine(job, comp, n, ctx=ctx, cp=cp, tus=tus,
-                          max_supersteps=int(a.get("max_supersteps", 200)))
+                          max_supersteps=int(a.get("max_supersteps", 200)),
+                          fused=_use_fused(a["fused_messages"], ctx.device))
     lo, hi = engine.local_vertex_range()
-    engine.set_graph(make_ring_plus_random_graph(
-        n, int(a["out_degree"]), lo, hi, ctx.device,
-        stable_seed(job.job_id, "graph")))   # rank-independent graph
+    if parsed is not None:
+        row_ptr, edge_dst, edge_w, _n, num_edges = dl.load_graph_partition(
+            a["input"], lo, hi, weighted, ctx.world_size, parsed=parsed)
+        graph = make_graph_from_edges(row_ptr, edge_dst, edge_w, lo, n,
+                                      ctx.device)
+    else:
+        graph = make_ring_plus_random_graph(
+            n, int(a["out_degree"]), lo, hi, ctx.device,
+            stable_seed(job.job_id, "graph"))   # rank-independent graph
+        num_edges = n * int(a["out_degree"])
+    engine.set_graph(graph)
     values = engine.run()
+    if a.get("output"):
+        _write_part(str(a["output"]), ctx.rank, lo, values)
     dt = time.perf_counter() - t0
     return {
         "job_id": job.job_id,
         "rank": ctx.rank,
         "num_batches": engine.supersteps_run,     # supersteps as "batches"
         "supersteps": engine.supersteps_run,
+        "num_vertices": n,
+        "num_edges": num_edges,
+        "fused_messages": engine.fused,
         "num_local_vertices": int(values.shape[0]),
         "total_examples": int(values.shape[0]) * engine.supersteps_run,
         "elapsed_sec": dt,
