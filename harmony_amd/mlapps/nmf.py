@@ -81,6 +81,21 @@ class NMFBatch:
             torch.arange(row_ptr.shape[0] - 1, device=col_idx.device),
             row_ptr[1:] - row_ptr[:-1])
         self.col_sorted = (perm, seg_ptr, row_of[perm])
+        # int32 copies of the static indices for ops.nmf_step, and whether
+        # the batch's L rows are one contiguous range (then the kernel reads
+        # self.L in place at row l_lo and the update is a single slice copy)
+        def i32(t):
+            return t.to(torch.int32).contiguous()
+
+        self.row_ptr32 = i32(row_ptr)
+        self.col_local32 = i32(self.col_local)
+        self.col_sorted32 = tuple(i32(t) for t in self.col_sorted)
+        n = self.num_examples
+        self.l_lo = int(l_rows[0]) if n else 0
+        self.l_contiguous = bool(n == 0 or (
+            int(l_rows[-1]) - self.l_lo == n - 1
+            and torch.equal(l_rows, torch.arange(
+                self.l_lo, self.l_lo + n, device=l_rows.device))))
 
 
 def make_batches(job: JobConfig, rank: int, device: torch.device,
@@ -210,14 +225,23 @@ class NMFTrainer(Trainer):
             R_buf = self.R_batch
 
             def body(b=b, R_buf=R_buf):
-                L_batch = self.L[b.l_rows]
-                lgrad, rgrad, sq = ops.nmf_grad(
-                    L_batch, R_buf, b.row_ptr, b.col_local, b.vals,
-                    self.a["lam"], col_sorted=b.col_sorted)
-                # local L update (worker-side SGD apply, same rule as the
+                # gradient + worker-side SGD apply (same rule as the
                 # server's; step from a device scalar so decay stays live)
-                self.L[b.l_rows] = (L_batch - self._step_t * lgrad).clamp_(
-                    0.0, self.a["max_val"])
+                # in one op; pass B reads the old L, so the new rows land
+                # in a scratch tensor and are copied in afterwards
+                n = b.num_examples
+                if b.l_contiguous:
+                    L_src, lo = self.L, b.l_lo
+                else:
+                    L_src, lo = self.L[b.l_rows], 0
+                L_new, rgrad, sq = ops.nmf_step(
+                    L_src, lo, n, R_buf, b.row_ptr32, b.col_local32, b.vals,
+                    b.col_sorted32, None, self._step_t, self.a["lam"],
+                    self.a["max_val"])
+                if b.l_contiguous:
+                    self.L[lo:lo + n].copy_(L_new)
+                else:
+                    self.L[b.l_rows] = L_new
                 self.rgrad = rgrad
                 self._sq_err += sq
 

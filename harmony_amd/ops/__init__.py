@@ -279,6 +279,42 @@ def nmf_grad(L: torch.Tensor, R: torch.Tensor, row_ptr: torch.Tensor,
     return lgrad, rgrad, (e * e).sum()
 
 
+def nmf_step(L: torch.Tensor, l_lo: int, n: int, R_src: torch.Tensor,
+             row_ptr: torch.Tensor, col: torch.Tensor, vals: torch.Tensor,
+             col_sorted, rsrc_of: Optional[torch.Tensor],
+             step: torch.Tensor, lam: float, max_val: float,
+             want_lgrad: bool = False):
+    """One NMF compute phase on the batch L[l_lo:l_lo+n]: the two-pass
+    gradient of nmf_grad(col_sorted=...) plus the worker-side update
+    L_new = clamp(L_batch - step * lgrad, 0, max_val) in the same kernel.
+
+    col [nnz] names, per nonzero, a row of R_src; col_sorted = (perm,
+    seg_ptr, row_sorted) is the column-sorted view with one segment per
+    rgrad row; rsrc_of [n_uniq] maps an rgrad row to its R_src row (None:
+    rgrad row j is R_src row j). So R_src is either the gathered
+    [n_uniq, k] tensor with local col, or any larger table with rsrc_of.
+    Index tensors are int32 on GPU. step is a 0-dim float tensor on L's
+    device. L is not modified.
+    Returns (L_new [n, k], rgrad [n_uniq, k], sq_err_sum[, lgrad])."""
+    perm, seg_ptr, row_sorted = col_sorted
+    if _use_hip(L):
+        return tuple(_hip.nmf_step(
+            L.contiguous(), int(l_lo), int(n), R_src.contiguous(), row_ptr,
+            col, vals.contiguous(), perm, seg_ptr, row_sorted, rsrc_of, step, float(lam), float(max_val),
+            bool(want_lgrad)))
+    L_batch = L[l_lo:l_lo + n]
+    lgrad, rgrad, sq = nmf_grad(L_batch, R_src, row_ptr.long(), col.long(),
+                                vals, lam)
+    if rsrc_of is not None:
+        rgrad = rgrad[rsrc_of.long()]
+    else:
+        rgrad = rgrad[:seg_ptr.shape[0] - 1]
+    L_new = (L_batch - step * lgrad).clamp_(0.0, max_val)
+    if want_lgrad:
+        return L_new, rgrad, sq, lgrad
+    return L_new, rgrad, sq
+
+
 # ---------------------------------------------------------------------------
 # K7: LDA collapsed Gibbs sampling over a doc block
 # ---------------------------------------------------------------------------

@@ -13,6 +13,12 @@ std::vector<torch::Tensor> nmf_grad_twopass(
     torch::Tensor L, torch::Tensor R, torch::Tensor row_ptr,
     torch::Tensor col_idx, torch::Tensor vals, torch::Tensor perm,
     torch::Tensor seg_ptr, torch::Tensor row_sorted, double lam);
+std::vector<torch::Tensor> nmf_step(
+    torch::Tensor L, int64_t l_lo, int64_t n, torch::Tensor R_src,
+    torch::Tensor row_ptr, torch::Tensor col, torch::Tensor vals,
+    torch::Tensor perm, torch::Tensor seg_ptr, torch::Tensor row_sorted,
+    c10::optional<torch::Tensor> rsrc_of, torch::Tensor step, double lam,
+    double max_val, bool want_lgrad);
 std::vector<torch::Tensor> mlr_fwd(torch::Tensor X, torch::Tensor W,
                                    torch::Tensor labels);
 torch::Tensor mlr_grad(torch::Tensor P, torch::Tensor X);
@@ -102,6 +108,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nmf_grad", &nmf_grad, "NMF sparse-batch gradient (K1+K2)");
   m.def("nmf_grad_twopass", &nmf_grad_twopass,
         "NMF gradient, segmented-reduce rgrad, no atomics (K1+K2)");
+  m.def("nmf_step", &nmf_step,
+        "NMF two-pass gradient with prefetch ring + fused L update (K1+K2)");
   m.def("mlr_fwd", &mlr_fwd,
         "fused MLR forward: X@W^T + softmax + grad + CE/acc (K4)");
   m.def("mlr_grad", &mlr_grad, "skinny-C gradient GEMM P^T @ X (K5)");

@@ -26,6 +26,104 @@ def bench(fn, iters=20, warmup=4):
     return ts[len(ts) // 2] * 1e3
 
 
+def bench_dev(fn, iters=20, warmup=4):
+    """Median device time (ms) of fn's launches, by device events."""
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), \
+            torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    ts.sort()
+    return ts[len(ts) // 2]
+
+
+def nmf_step_ab(L, R, uniq, m, row_ptr, col_g, col, vals, perm, seg_ptr,
+                row_sorted):
+    """Whole compute phase (gradient + L update), legacy composition against
+    ops.nmf_step, R gathered ([n_uniq, k], local ids) or
+    indexed (the whole table, global ids). Row bytes: each pass gathers
+    nnz rows of 4*k bytes; TB/s is both passes' row bytes over the time."""
+    n, k = L.shape
+    nnz = col.shape[0]
+    row_bytes = 2 * nnz * 4 * k
+    step_t = torch.tensor(0.01, device="cuda")
+    table = torch.rand(m, k, device="cuda")
+    table[uniq] = R
+    i32 = torch.int32
+    cs32 = (perm.to(i32), seg_ptr.to(i32), row_sorted.to(i32))
+    row_ptr32, col32, col_g32, uniq32 = (row_ptr.to(i32), col.to(i32),
+                                         col_g.to(i32), uniq.to(i32))
+    Lw = L.clone()
+
+    def legacy():
+        lg, rg, sq = hip.nmf_grad_twopass(L, R, row_ptr, col, vals, perm,
+                                          seg_ptr, row_sorted, 0.0)
+        Lw[:] = (L - step_t * lg).clamp_(0.0, 1e6)
+
+    def legacy_with_gathers():
+        Rg = table[uniq]
+        Lb = L[l_rows]
+        lg, rg, sq = hip.nmf_grad_twopass(Lb, Rg, row_ptr, col, vals, perm,
+                                          seg_ptr, row_sorted, 0.0)
+        Lw[l_rows] = (Lb - step_t * lg).clamp_(0.0, 1e6)
+
+    l_rows = torch.arange(n, device="cuda")
+    cases = {"legacy twopass + torch L chain": legacy,
+             "legacy incl. R and L gathers": legacy_with_gathers}
+    if hasattr(hip, "nmf_step"):
+        def gathered():
+            Ln, rg, sq = hip.nmf_step(L, 0, n, R, row_ptr32, col32, vals,
+                                      *cs32, None, step_t, 0.0, 1e6,
+                                      False)
+            Lw.copy_(Ln)
+
+        def gathered_with_gather():
+            Ln, rg, sq = hip.nmf_step(L, 0, n, table[uniq], row_ptr32,
+                                      col32, vals, *cs32, None, step_t,
+                                      0.0, 1e6, False)
+            Lw.copy_(Ln)
+
+        def indexed():
+            Ln, rg, sq = hip.nmf_step(L, 0, n, table, row_ptr32, col_g32,
+                                      vals, *cs32, uniq32, step_t, 0.0,
+                                      1e6, False)
+            Lw.copy_(Ln)
+
+        cases["nmf_step gathered R"] = gathered
+        cases["nmf_step gathered R incl. gather"] = \
+            gathered_with_gather
+        cases["nmf_step indexed R"] = indexed
+    res = {kk: [] for kk in cases}
+    for _ in range(3):
+        for kk, fn in cases.items():
+            res[kk].append(bench_dev(fn))
+    print(f"row bytes per compute phase: {row_bytes / 1e6:.0f} MB")
+    for kk, tt in res.items():
+        t = min(tt)
+        print(f"{kk:42s} {t * 1e3:8.1f} us  {row_bytes / t / 1e9:6.2f} TB/s "
+              f"(runs: {[f'{x * 1e3:.0f}' for x in tt]})")
+
+
+def scatter_apply_ab():
+    """Owner-side nmf_sgd apply at the bench shape: 65536 rows x 100."""
+    n, vd = 65536, 100
+    shard = torch.rand(n, vd, device="cuda")
+    rows = torch.randperm(n, device="cuda")
+    deltas = torch.randn(n, vd, device="cuda")
+    moved = 3 * n * vd * 4 + n * 8       # read shard+delta, write shard, rows
+    tt = [bench_dev(lambda: hip.scatter_apply(shard, rows, deltas, 2, 0.01,
+                                              1e6)) for _ in range(3)]
+    t = min(tt)
+    print(f"scatter_apply 65536x100 (this build)       {t * 1e3:8.1f} us  "
+          f"{moved / 1e6:.0f} MB  {moved / t / 1e9:6.2f} TB/s")
+
+
 def main():
     torch.manual_seed(0)
     # bench default shapes: 16384 rows x 128 nnz, rank 100, 65536 cols
@@ -51,6 +149,11 @@ def main():
         "nmf_twopass": lambda: hip.nmf_grad_twopass(
             L, R, row_ptr, col, vals, perm, seg_ptr, row_sorted, 0.0),
     }
+    nmf_step_ab(L, R, uniq, m, row_ptr, col_g, col, vals, perm, seg_ptr,
+                row_sorted)
+    scatter_apply_ab()
+    if "--step-only" in sys.argv:
+        return
     # LDA: bench default 8192 docs x 128 tokens, K=256, V=100k, Zipf sorted
     D, T, K, V = 8192, 128, 256, 100000
     g = torch.Generator().manual_seed(1)
