@@ -95,6 +95,41 @@ def parse_libsvm(lines, num_features: int
     return X, torch.tensor(ys)
 
 
+def parse_libsvm_csr(lines, num_features: int
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                torch.Tensor]:
+    """-> CSR (row_ptr int64 [n+1], col int32 [nnz], val float32 [nnz],
+    y float32 [n]) for inputs whose feature space is too wide to densify
+    (reference MLRETDataParser builds SparseVectors). Neither time nor
+    memory depends on num_features.
+
+    Densified, the result equals the dense parsers' output: indices outside
+    [0, num_features) are dropped, '#' and blank lines are skipped, entries
+    keep file order within a row, and a repeated index keeps its LAST value
+    (at the position of its first occurrence), so each (row, col) appears
+    once. A row with no features is kept; its row_ptr entries are equal."""
+    row_ptr, cols, vals, ys = [0], [], [], []
+    for ln in lines:
+        ln = ln.strip()
+        if not ln or ln.startswith("#"):
+            continue
+        toks = ln.split()
+        ys.append(float(toks[0]))
+        row = {}
+        for tok in toks[1:]:
+            i, v = tok.split(":")
+            i = int(i)
+            if 0 <= i < num_features:
+                row[i] = float(v)
+        cols.extend(row.keys())
+        vals.extend(row.values())
+        row_ptr.append(len(cols))
+    return (torch.tensor(row_ptr, dtype=torch.int64),
+            torch.tensor(cols, dtype=torch.int32),
+            torch.tensor(vals, dtype=torch.float32),
+            torch.tensor(ys, dtype=torch.float32))
+
+
 def parse_lda(lines) -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (doc_offsets [n+1], word_ids flat) — one doc per line."""
     offsets = [0]
@@ -180,6 +215,28 @@ def parse_libsvm_split(path: str, rank: int, world_size: int,
         return tuple(nat.parse_libsvm_bytes(buf,
                                             num_features))
     return parse_libsvm(read_split(path, split), num_features)
+
+
+def parse_libsvm_csr_bytes(buf: bytes, num_features: int):
+    """Native, threaded CSR parse of raw libsvm-style bytes (same result as
+    parse_libsvm_csr on the same lines). Needs the built extension."""
+    nat = _native()
+    if nat is None:
+        raise RuntimeError("parse_libsvm_csr_bytes needs the native "
+                           "extension (run: python setup_ops.py build)")
+    return tuple(nat.parse_libsvm_csr_bytes(buf, num_features))
+
+
+def parse_libsvm_csr_split(path: str, rank: int, world_size: int,
+                           num_features: int):
+    """This rank's split of a libsvm-style file as CSR (native parser when
+    the extension is built, else Python; same result either way)."""
+    split = compute_splits(path, world_size)[rank]
+    nat = _native(world_size)
+    if nat is not None:
+        buf = _read_split_bytes(path, split)
+        return tuple(nat.parse_libsvm_csr_bytes(buf, num_features))
+    return parse_libsvm_csr(read_split(path, split), num_features)
 
 
 def parse_lda_split(path: str, rank: int, world_size: int):

@@ -14,7 +14,11 @@ add-update epilogue. GEMMs go to rocBLAS (torch.matmul); the softmax+grad
 scaling is the fused HIP kernel `mlr_softmax_grad` (ops/csrc/mlr.hip).
 
 App args: num_classes, num_features, num_parts_per_class, batch_size,
-step_size, lambda (L2), dtype.
+step_size, lambda (L2), dtype; sparse (default false) keeps every batch as a
+SparseBatch (CSR + static column index) and runs the K4s gather-reduce
+kernels (ops/csrc/mlr_sparse.hip) instead of the dense GEMM pair, so the
+input's feature space may be far wider than a row is long; nnz_per_row sizes
+the synthetic sparse generator.
 """
 
 from __future__ import annotations
@@ -26,6 +30,7 @@ from harmony_amd.dolphin.data_provider import TrainingDataProvider
 from harmony_amd.dolphin.model_accessor import ETModelAccessor
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
 from harmony_amd.et.table import Table
+from harmony_amd.mlapps.sparse_batch import SparseBatch
 from harmony_amd import ops
 
 MODEL_TABLE = "mlr_model"
@@ -34,9 +39,13 @@ MODEL_TABLE = "mlr_model"
 def defaults(job: JobConfig) -> dict:
     a = dict(num_classes=10, num_features=1024, num_parts_per_class=8,
              batch_size=4096, step_size=0.01, lam=1e-4, dtype="float32",
-             decay_rate=0.9, decay_period=5)
+             decay_rate=0.9, decay_period=5, sparse="false", nnz_per_row=32)
     a.update(job.app_args)
     return a
+
+
+def _is_sparse(a: dict) -> bool:
+    return str(a.get("sparse", "")).lower() in ("true", "1")
 
 
 def model_table_cfg(job: JobConfig, world_size: int) -> TableConfig:
@@ -65,6 +74,8 @@ def make_batches(job: JobConfig, rank: int, device: torch.device,
     a sample_mlr-format file; otherwise synthetic per-class gaussian blobs,
     deterministic per (job, rank)."""
     a = defaults(job)
+    if _is_sparse(a):
+        return _make_sparse_batches(job, a, rank, device, world_size)
     if a.get("input") or job.app_args.get("input"):
         from harmony_amd import dataloader as dl
 
@@ -84,6 +95,50 @@ def make_batches(job: JobConfig, rank: int, device: torch.device,
     for _ in range(n_blocks):
         y = torch.randint(0, C, (B,), generator=g)
         x = centers[y] + torch.randn(B, F, generator=g)
+        blocks.append((x.to(device), y.to(device)))
+    return blocks
+
+
+def _make_sparse_batches(job: JobConfig, a: dict, rank: int,
+                         device: torch.device, world_size: int):
+    """make_batches for sparse=true: the same block structure as the dense
+    branch, every block a (SparseBatch, labels) pair. No tensor with B*F
+    elements is built on either path."""
+    F = int(a["num_features"])
+    n_blocks = max(1, job.num_worker_blocks or job.num_mini_batches)
+    blocks = []
+    if a.get("input"):
+        from harmony_amd import dataloader as dl
+
+        row_ptr, col, val, y = dl.parse_libsvm_csr_split(
+            a["input"], rank, world_size, F)
+        n = y.shape[0]
+        # torch.chunk's row ranges, so block i holds the rows the dense
+        # branch would give it
+        size = -(-n // n_blocks) if n else 0
+        for lo in range(0, max(1, n), max(1, size)):
+            hi = min(n, lo + size)
+            e0, e1 = int(row_ptr[lo]), int(row_ptr[hi])
+            x = SparseBatch(row_ptr[lo:hi + 1] - e0, col[e0:e1],
+                            val[e0:e1], F)
+            blocks.append((x.to(device), y[lo:hi].long().to(device)))
+        return blocks
+    C, B = a["num_classes"], a["batch_size"]
+    k = max(1, min(int(a["nnz_per_row"]), F))
+    from harmony_amd.utils import stable_seed
+
+    g = torch.Generator().manual_seed(stable_seed(job.job_id, rank))
+    centers = torch.randn(C, F, generator=g) * 0.5
+    for _ in range(n_blocks):
+        y = torch.randint(0, C, (B,), generator=g)
+        # per-row random feature subset: k draws, sorted, repeats dropped
+        cols = torch.randint(0, F, (B, k), generator=g).sort(dim=1).values
+        keep = torch.ones((B, k), dtype=torch.bool)
+        keep[:, 1:] = cols[:, 1:] != cols[:, :-1]
+        vals = centers[y.unsqueeze(1), cols] + torch.randn(B, k, generator=g)
+        row_ptr = torch.zeros(B + 1, dtype=torch.int64)
+        row_ptr[1:] = torch.cumsum(keep.sum(dim=1), 0)
+        x = SparseBatch(row_ptr, cols[keep].to(torch.int32), vals[keep], F)
         blocks.append((x.to(device), y.to(device)))
     return blocks
 
@@ -137,6 +192,32 @@ class MLRTrainer(Trainer):
                                    device=self.ctx.device)
         return self._wt
 
+    def _sparse_wt_buf(self):
+        # persistent [F, Cp] W^T buffer for the K4s forward, refilled from
+        # the pulled model once per batch; the CPU reference reads W itself
+        if self.ctx.device.type != "cuda":
+            return None
+        if getattr(self, "_sparse_wt", None) is None:
+            C, F = self.a["num_classes"], self.a["num_features"]
+            self._sparse_wt = torch.zeros((F, (C + 3) // 4 * 4),
+                                          dtype=torch.float32,
+                                          device=self.ctx.device)
+        return self._sparse_wt
+
+    def _sparse_compute(self, x: SparseBatch, y: torch.Tensor) -> None:
+        # same math as the dense body with both GEMMs replaced by the K4s
+        # gather-reduces; graphs and the MFMA path do not apply here
+        W = self._w_matrix()
+        F = self.a["num_features"]
+        p, loss, correct = ops.mlr_sparse_forward(
+            x.row_ptr, x.col, x.val, W, y, Wt_buf=self._sparse_wt_buf())
+        g = ops.mlr_sparse_grad(x.feat_ids, x.feat_ptr, x.feat_row,
+                                x.feat_val, p, F)            # [C, F]
+        self.grad_raw = g / x.shape[0] + self.a["lam"] * W
+        self._loss_sum += loss
+        self._correct += correct
+        self._loss_n += x.shape[0]
+
     def pull_model(self) -> None:
         C, P = self.a["num_classes"], self.a["num_parts_per_class"]
         pulled = self.accessor.pull_all()[:C * P]
@@ -150,6 +231,9 @@ class MLRTrainer(Trainer):
         x, y = self.batch
         if x.shape[0] == 0:       # stopped worker: zero grad, no forward
             self.grad_raw = torch.zeros_like(self._w_matrix())
+            return
+        if isinstance(x, SparseBatch):
+            self._sparse_compute(x, y)
             return
         key = id(self.batch)
         body = self._bodies.get(key)
@@ -239,6 +323,8 @@ def build(job: JobConfig, ctx, cp):
         # frac<=0 -> EMPTY batch: a stopped worker (StopWorkerOp) does
         # zero work and its sparse pulls/pushes carry zero keys
         n = 0 if frac <= 0 else max(1, int(b[0].shape[0] * frac))
+        if isinstance(b[0], SparseBatch):
+            return (b[0].prefix(n), b[1][:n])
         return (b[0][:n], b[1][:n])
 
     provider = TrainingDataProvider(reslice=_reslice, local_blocks=

@@ -12,6 +12,7 @@ Kernel inventory (reference hot loops):
   K1  nmf_grad            NMFTrainer.java:328-367
   K3  (fused in push)     NMFETModelUpdateFunction.java:48-52
   K4  mlr softmax+grad    MLRTrainer.java:374-398,475-489
+  K4s mlr_sparse_fwd/grad MLRTrainer.java:374-398 over SparseVector rows
   K7  lda_gibbs           SparseLDASampler.java:141-274
   K9  scatter-apply       LDAETModelUpdateFunction.java:43-64
   K12 loss reductions     NMFTrainer.java:414-456 etc.
@@ -235,6 +236,138 @@ def softmax_grad_ce(logits: torch.Tensor, labels: torch.Tensor
     grad.scatter_add_(1, labels.view(-1, 1),
                       torch.full((z.shape[0], 1), -1.0, device=z.device))
     return grad.to(logits.dtype), loss, correct
+
+
+# ---------------------------------------------------------------------------
+# K4s: sparse MLR — CSR forward and column-index gradient (gather-reduce)
+# ---------------------------------------------------------------------------
+
+def mlr_sparse_group(num_segments: int, num_entries: int) -> int:
+    """Lanes that cooperate on one segment (a row in the forward, a present
+    feature in the gradient) of the K4s kernel: the smallest power of two >=
+    an eighth of the mean segment length, clamped to 1..64. K13's rule with
+    up to 8 entries per lane instead of 1: an entry here costs a Cp-float
+    row fetch and every doubling of the group adds Cp shuffles per segment.
+    Measured against forced groups it picks the fastest or a near-fastest
+    group at 1.3, 32, 150 and 780 entries per segment, and one up to 1.4x
+    off the fastest at 254 (profiles/mlr_sparse_ab.md). A function of the
+    batch alone, so a batch always runs with the same summation order."""
+    mean = num_entries / max(1, num_segments)
+    g = 1
+    while g < 64 and g * 8 < mean:
+        g *= 2
+    return g
+
+
+def mlr_sparse_wt(W: torch.Tensor, out: Optional[torch.Tensor] = None
+                  ) -> torch.Tensor:
+    """The model transposed and padded for the K4s forward: [F, Cp] float32,
+    Cp = C rounded up to a multiple of 4, pad columns zero. `out` is a
+    persistent buffer from an earlier call (its pad columns stay zero)."""
+    C, F = W.shape
+    if out is None:
+        out = torch.zeros((F, (C + 3) // 4 * 4), dtype=torch.float32,
+                          device=W.device)
+    out[:, :C] = W.t()
+    return out
+
+
+def mlr_sparse_logits(row_ptr: torch.Tensor, col: torch.Tensor,
+                      val: torch.Tensor, W: torch.Tensor,
+                      Wt_buf: Optional[torch.Tensor] = None,
+                      _force_group: int = 0) -> torch.Tensor:
+    """logits [B, C] = X @ W^T for a CSR batch X (row_ptr int64 [B+1],
+    col int32 [nnz], val float32 [nnz]) and the model W [C, F], touching
+    only the batch's non-zeros (K4s forward, ops/csrc/mlr_sparse.hip;
+    reference MLRTrainer.java:374-398 over SparseVector rows). A row with
+    no entries gives zeros; entries whose column lies outside [0, F) are
+    skipped.
+
+    On GPU the kernel reads W through mlr_sparse_wt's layout; Wt_buf is the
+    caller's persistent buffer for it (filled here), else one is allocated.
+    CPU tensors (and HARMONY_FORCE_TORCH_OPS=1) take the torch reference
+    below, which is also the kernel's test oracle. _force_group is for
+    tests: it overrides the lanes-per-row choice of mlr_sparse_group."""
+    C, F = W.shape
+    B = row_ptr.shape[0] - 1
+    if _use_hip(W):
+        if B == 0:
+            return torch.empty((0, C), dtype=torch.float32, device=W.device)
+        group = _force_group or mlr_sparse_group(B, col.shape[0])
+        Wt = mlr_sparse_wt(W, Wt_buf)
+        return _hip.mlr_sparse_fwd(row_ptr.contiguous(), col.contiguous(),
+                                   val.contiguous(), Wt, int(C), int(group))
+    dev = W.device
+    row = torch.repeat_interleave(torch.arange(B, device=dev),
+                                  row_ptr[1:] - row_ptr[:-1])
+    c = col.long()
+    ok = (c >= 0) & (c < F)
+    row, c, v = row[ok], c[ok], val[ok]
+    logits = torch.zeros((B, C), dtype=torch.float32, device=dev)
+    logits.index_add_(0, row, v.unsqueeze(1) * W.float().t()[c])
+    return logits
+
+
+def mlr_sparse_forward(row_ptr: torch.Tensor, col: torch.Tensor,
+                       val: torch.Tensor, W: torch.Tensor,
+                       labels: torch.Tensor,
+                       Wt_buf: Optional[torch.Tensor] = None,
+                       _force_group: int = 0
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Sparse MLR forward: mlr_sparse_logits, then the fused softmax +
+    label-subtract + CE/accuracy kernel (K4). Same return contract as
+    mlr_forward: (p - onehot [B, C], loss_sum, n_correct)."""
+    return softmax_grad_ce(
+        mlr_sparse_logits(row_ptr, col, val, W, Wt_buf, _force_group),
+        labels)
+
+
+def mlr_sparse_grad(feat_ids: torch.Tensor, feat_ptr: torch.Tensor,
+                    feat_row: torch.Tensor, feat_val: torch.Tensor,
+                    P: torch.Tensor, F: int, _force_group: int = 0
+                    ) -> torch.Tensor:
+    """grad [C, F] = P^T @ X through the batch's static column index (K4s
+    gradient): feat_ids int32 [nf] the distinct present columns ascending,
+    feat_ptr int64 [nf+1], feat_row int32 [nnz] / feat_val float32 [nnz]
+    the entries of each feature with rows ascending. G[c, f] =
+    sum_e feat_val[e] * P[feat_row[e], c]; absent features stay exactly 0.
+    No atomics, so the result is bitwise reproducible. The kernel reads P
+    rows with 16-byte loads, so a P whose row stride is no multiple of 4
+    floats is first copied into a padded [B, Cp] buffer (measured faster
+    than scalar loads, the copy included). Entries whose row lies outside
+    [0, B), and features outside [0, F), are skipped.
+
+    CPU tensors (and HARMONY_FORCE_TORCH_OPS=1) take the torch reference
+    below. _force_group overrides the lanes-per-feature choice (tests)."""
+    B, C = P.shape
+    nf = feat_ids.shape[0]
+    if _use_hip(P):
+        if B == 0 or nf == 0:
+            return torch.zeros((C, F), dtype=torch.float32, device=P.device)
+        group = _force_group or mlr_sparse_group(nf, feat_row.shape[0])
+        Cp = (C + 3) // 4 * 4
+        if (P.dtype != torch.float32 or P.stride(1) != 1 or P.stride(0) % 4
+                or P.stride(0) < Cp or P.data_ptr() % 16):
+            Ppad = torch.zeros((B, Cp), dtype=torch.float32, device=P.device)
+            Ppad[:, :C] = P
+            P = Ppad[:, :C]
+        return _hip.mlr_sparse_grad(
+            feat_ids.contiguous(), feat_ptr.contiguous(),
+            feat_row.contiguous(), feat_val.contiguous(), P, int(F),
+            int(group))
+    dev = P.device
+    seg = torch.repeat_interleave(torch.arange(nf, device=dev),
+                                  feat_ptr[1:] - feat_ptr[:-1])
+    r = feat_row.long()
+    ok = (r >= 0) & (r < B)
+    seg, r, v = seg[ok], r[ok], feat_val[ok]
+    per_feat = torch.zeros((nf, C), dtype=torch.float32, device=dev)
+    per_feat.index_add_(0, seg, v.unsqueeze(1) * P.float()[r])
+    G = torch.zeros((C, F), dtype=torch.float32, device=dev)
+    f = feat_ids.long()
+    okf = (f >= 0) & (f < F)
+    G[:, f[okf]] = per_feat[okf].t()
+    return G
 
 
 # ---------------------------------------------------------------------------

@@ -93,6 +93,8 @@ void dense_apply(torch::Tensor shard, torch::Tensor delta, int64_t mode,
 std::vector<torch::Tensor> parse_nmf_bytes(const std::string& buf);
 std::vector<torch::Tensor> parse_libsvm_bytes(const std::string& buf,
                                               int64_t num_features);
+std::vector<torch::Tensor> parse_libsvm_csr_bytes(const std::string& buf,
+                                                  int64_t num_features);
 std::vector<torch::Tensor> parse_lda_bytes(const std::string& buf);
 std::vector<torch::Tensor> parse_graph_bytes(const std::string& buf,
                                              bool weighted);
@@ -101,6 +103,12 @@ std::vector<torch::Tensor> pregel_pull(
     c10::optional<torch::Tensor> in_w, double w_const, torch::Tensor vert_msg,
     c10::optional<torch::Tensor> send_mask, int64_t combiner, bool add_weight,
     int64_t group);
+torch::Tensor mlr_sparse_fwd(torch::Tensor row_ptr, torch::Tensor col,
+                             torch::Tensor val, torch::Tensor Wt, int64_t C,
+                             int64_t group);
+torch::Tensor mlr_sparse_grad(torch::Tensor feat_ids, torch::Tensor feat_ptr,
+                              torch::Tensor feat_row, torch::Tensor feat_val,
+                              torch::Tensor P, int64_t F, int64_t group);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlr_softmax_grad", &mlr_softmax_grad,
@@ -152,10 +160,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("parse_nmf_bytes", &parse_nmf_bytes, "native NMF text parser");
   m.def("parse_libsvm_bytes", &parse_libsvm_bytes,
         "native libsvm-style parser (mlr/gbt/lasso)");
+  m.def("parse_libsvm_csr_bytes", &parse_libsvm_csr_bytes,
+        "native libsvm-style parser to CSR (sparse mlr)");
   m.def("parse_lda_bytes", &parse_lda_bytes, "native LDA doc parser");
   m.def("parse_graph_bytes", &parse_graph_bytes,
         "native adjacency-list parser (pagerank / shortestpath)");
   m.def("pregel_pull", &pregel_pull,
         "Pregel send+combine as a CSR gather-reduce over the pull index "
         "(K13)");
+  m.def("mlr_sparse_fwd", &mlr_sparse_fwd,
+        "sparse MLR logits: CSR gather-reduce over W^T rows (K4s)");
+  m.def("mlr_sparse_grad", &mlr_sparse_grad,
+        "sparse MLR gradient through the batch's column index (K4s)");
 }

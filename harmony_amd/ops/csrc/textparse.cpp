@@ -7,6 +7,7 @@
 
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cctype>
 #include <cstdint>
@@ -177,6 +178,107 @@ std::vector<torch::Tensor> parse_libsvm_bytes(const std::string& buf,
     off += n;
   }
   return {X, y};
+}
+
+// "label idx:val idx:val ..." -> CSR (row_ptr int64 [n+1], col int32 [nnz],
+// val float32 [nnz], y float32 [n]). Same row rules as parse_libsvm_bytes
+// (indices outside [0, num_features) dropped, a repeated index keeps its
+// last value) but neither time nor memory depends on num_features: entries
+// stay in file order, and a repeated index keeps the position of its first
+// occurrence with the value of its last, so each (row, col) appears once.
+std::vector<torch::Tensor> parse_libsvm_csr_bytes(const std::string& buf,
+                                                  int64_t num_features) {
+  TORCH_CHECK(num_features >= 0 && num_features < ((int64_t)1 << 31),
+              "num_features must be below 2^31");
+  const int T = nthreads();
+  auto chunks = line_chunks(buf.data(), (int64_t)buf.size(), T);
+  std::vector<std::vector<int32_t>> cols(T);
+  std::vector<std::vector<float>> vals(T), ys(T);
+  std::vector<std::vector<int64_t>> lens(T);
+  std::vector<std::thread> ths;
+  for (int t = 0; t < T; ++t) {
+    ths.emplace_back([&, t] {
+      Cursor c{chunks[t].first, chunks[t].second};
+      auto& cs = cols[t];
+      auto& vs = vals[t];
+      std::vector<std::pair<int32_t, int64_t>> order;   // (col, position)
+      while (!c.done()) {
+        if (c.at_comment_or_empty()) { c.next_line(); continue; }
+        double lab = c.read_double();
+        const size_t base = cs.size();
+        bool ascending = true;
+        while (!c.eol()) {
+          long idx = c.read_long();
+          c.skip_ws_inline();
+          if (c.p < c.end && *c.p == ':') ++c.p;
+          double v = c.read_double();
+          if (idx < 0 || idx >= num_features) continue;
+          if (cs.size() > base && (int32_t)idx <= cs.back())
+            ascending = false;
+          cs.push_back((int32_t)idx);
+          vs.push_back((float)v);
+        }
+        if (!ascending) {
+          // only an unsorted row can repeat an index: sort (col, position)
+          // pairs, move each run's last value to its first position and
+          // drop the rest
+          order.clear();
+          for (size_t i = base; i < cs.size(); ++i)
+            order.emplace_back(cs[i], (int64_t)i);
+          std::sort(order.begin(), order.end());
+          bool dup = false;
+          for (size_t i = 0; i < order.size();) {
+            size_t j = i + 1;
+            while (j < order.size() && order[j].first == order[i].first) ++j;
+            if (j > i + 1) {
+              dup = true;
+              vs[order[i].second] = vs[order[j - 1].second];
+              for (size_t k = i + 1; k < j; ++k) cs[order[k].second] = -1;
+            }
+            i = j;
+          }
+          if (dup) {
+            size_t w = base;
+            for (size_t i = base; i < cs.size(); ++i)
+              if (cs[i] >= 0) { cs[w] = cs[i]; vs[w] = vs[i]; ++w; }
+            cs.resize(w);
+            vs.resize(w);
+          }
+        }
+        lens[t].push_back((int64_t)(cs.size() - base));
+        ys[t].push_back((float)lab);
+        c.next_line();
+      }
+    });
+  }
+  for (auto& th : ths) th.join();
+  int64_t n = 0, nnz = 0;
+  for (int t = 0; t < T; ++t) {
+    n += (int64_t)ys[t].size();
+    nnz += (int64_t)cols[t].size();
+  }
+  auto rp = torch::empty({n + 1}, torch::kInt64);
+  auto co = torch::empty({nnz}, torch::kInt32);
+  auto vo = torch::empty({nnz}, torch::kFloat32);
+  auto y = torch::empty({n}, torch::kFloat32);
+  auto* rpp = rp.data_ptr<int64_t>();
+  rpp[0] = 0;
+  int64_t r = 0, off = 0;
+  for (int t = 0; t < T; ++t) {
+    const int64_t m = (int64_t)cols[t].size();
+    if (m) {
+      std::memcpy(co.data_ptr<int32_t>() + off, cols[t].data(), m * 4);
+      std::memcpy(vo.data_ptr<float>() + off, vals[t].data(), m * 4);
+    }
+    off += m;
+    if (!ys[t].empty())
+      std::memcpy(y.data_ptr<float>() + r, ys[t].data(), ys[t].size() * 4);
+    for (int64_t L : lens[t]) {
+      rpp[r + 1] = rpp[r] + L;
+      ++r;
+    }
+  }
+  return {rp, co, vo, y};
 }
 
 // "word word word ..." one doc per line -> (doc_offsets [n+1], words)
