@@ -41,7 +41,10 @@ def defaults(job: JobConfig) -> dict:
              tokens_per_doc=64, alpha=0.1, beta=0.01, docs_per_batch=4096,
              sampler="exact",   # "exact" (dense Gibbs) | "alias" (MH, K7b)
                                 # | "alias_wave" (K7c wave-per-doc MH)
-             alias_refresh=4)   # rebuild alias tables every N pulls
+             alias_refresh=4,   # rebuild alias tables every N pulls
+             packed=True)       # alias_wave: packed per-segment tables (K7d)
+                                # when K/64 is 1, 2, 4 or 8; False keeps the
+                                # legacy arrays and kernels
     a.update(job.app_args)
     return a
 
@@ -194,7 +197,51 @@ class LDATrainer(Trainer):
         self.batch = batch
         self._block_idx = batch.block_idx
 
+    def _use_packed(self) -> bool:
+        return (self.a["sampler"] == "alias_wave"
+                and str(self.a["packed"]).lower() not in ("false", "0")
+                and ops.lda_packed_supported(self.a["num_topics"]))
+
+    def _single_owner(self) -> bool:
+        from harmony_amd.et.onesided import OneSidedTable
+
+        table = self.accessor.table
+        return (not isinstance(table, OneSidedTable)
+                and (table.comm is None or table.world_size == 1))
+
+    def _packed_tables(self, b):
+        """Per-block packed tables and the block's static index arrays."""
+        if not hasattr(self, "_packed"):
+            self._packed = {}
+        bid = self._block_idx
+        if bid not in self._packed:
+            self._packed[bid] = ops.lda_packed_alloc(
+                b.uniq_words.shape[0], self.a["num_topics"], self.ctx.device)
+        if not hasattr(b, "word_local32"):
+            b.word_local32 = b.word_local.to(torch.int32)
+        return self._packed[bid]
+
     def pull_model(self) -> None:
+        if self._use_packed() and self._single_owner():
+            # single owner: one gather of the batch's word rows through
+            # row indices cached per block. The summary row is not copied:
+            # the alias build (COMP phase) reads it, and the word rows, from
+            # the shard in place, which is safe because nothing writes this
+            # table between here and the sweep.
+            import time
+
+            t0 = time.perf_counter()
+            b = self.batch
+            table = self.accessor.table
+            if not hasattr(b, "row_of_local"):
+                rows = table.local_rows_of(b.uniq_words)
+                b.rows64 = rows
+                b.row_of_local = rows.to(torch.int32)
+                b.summary_row = int(table.local_rows_of(b.pull_keys[-1:]))
+            self.word_topic = table.shard[b.rows64]
+            self.accessor.metrics["total_pull_time_sec"] += \
+                time.perf_counter() - t0
+            return
         pulled = self.accessor.pull(self.batch.pull_keys)
         from harmony_amd.dolphin.model_accessor import OneSidedAccessor
 
@@ -233,7 +280,62 @@ class LDATrainer(Trainer):
         self._alias_age[bid] = age + 1
         self._alias = self._alias_cache[bid]
 
+    def _ensure_alias_packed(self, rec, top, fused: bool) -> None:
+        # same refresh schedule as _ensure_alias; only invden is kept
+        # beside the packed tables
+        if not hasattr(self, "_invden_cache"):
+            self._invden_cache = {}
+            self._alias_age = {}
+        bid = self._block_idx
+        refresh = max(1, int(self.a["alias_refresh"]))
+        age = self._alias_age.get(bid, refresh)
+        if age >= refresh:
+            if fused:
+                b = self.batch
+                shard = self.accessor.table.shard
+                src, rows, nk = shard, b.row_of_local, shard[b.summary_row]
+            else:
+                src, rows, nk = self.word_topic, None, self.topic_sum
+            self._invden_cache[bid], _ = ops.lda_alias_build_packed(
+                src, rows, nk, self.a["beta"], self.a["num_vocabs"], rec, top)
+            age = 0
+        self._alias_age[bid] = age + 1
+
+    def _local_compute_packed(self) -> None:
+        b = self.batch
+        z = self._assignments[self._block_idx]
+        fused = self._single_owner()
+        self._step += 1
+        if b.docs_contiguous:
+            dt = self.doc_topic[b.doc_lo:b.doc_lo + b.num_examples]
+        else:
+            dt = self.doc_topic[b.doc_ids]      # gather copy
+        rec, top = self._packed_tables(b)
+        self._ensure_alias_packed(rec, top, fused)
+        invden = self._invden_cache[self._block_idx]
+        seed = self._epoch_seed + self._step
+        if fused:
+            # the sweep applies its own +/-1 to the shard: no copy of the
+            # old assignments, nothing left for push_update
+            ops.lda_mh_wave_packed(
+                dt, self.word_topic, rec, top, invden, b.doc_offsets,
+                b.word_local32, z, self.a["alpha"], self.a["beta"], seed,
+                shard=self.accessor.table.shard,
+                row_of_local=b.row_of_local, summary_row=b.summary_row)
+            self._old_z = None
+        else:
+            self._old_z = z.clone()
+            ops.lda_mh_wave_packed(
+                dt, self.word_topic, rec, top, invden, b.doc_offsets,
+                b.word_local32, z, self.a["alpha"], self.a["beta"], seed)
+        if not b.docs_contiguous:
+            self.doc_topic[b.doc_ids] = dt      # write back
+        self._new_z = z
+
     def local_compute(self) -> None:
+        if self._use_packed():
+            self._local_compute_packed()
+            return
         b = self.batch
         z = self._assignments[self._block_idx]
         old = z.clone()
@@ -274,6 +376,9 @@ class LDATrainer(Trainer):
         table = self.accessor.table
         b = self.batch
         old, z = self._old_z, self._new_z
+        if old is None:
+            # fused sweep (single-owner packed path) already applied it
+            return
         from harmony_amd.et.onesided import OneSidedTable
 
         if isinstance(table, OneSidedTable):

@@ -549,8 +549,11 @@ def _vose_serial(pr, al, lk, n):
         small_top = lk[sm]
         lg = large_top
         al[sm] = lg
-        rem = float(pr[lg]) + float(pr[sm]) - 1.0
-        pr[lg] = rem
+        # float32 at every step, as on the device: summed in double and
+        # rounded once, the remainder can land one ulp off the kernel's
+        rem_t = (pr[lg] + pr[sm]) - 1.0
+        pr[lg] = rem_t
+        rem = float(rem_t)
         large_top = lk[lg]
         if rem < 1.0:
             lk[lg] = small_top
@@ -588,11 +591,17 @@ def lda_alias_build(word_topic: torch.Tensor, topic_sum: torch.Tensor,
     assert K % W == 0, "alias sampler requires K % 64 == 0"
     S = K // W
     invden = (1.0 / (topic_sum.float() + num_vocabs * beta)).contiguous()
-    p = (word_topic.float() + beta) * invden            # [rows, K]
+    c = word_topic.float() + beta
+    p = c * invden                                       # [rows, K]
     pseg = p.view(rows, W, S)
+    # the kernel accumulates the segment mass with a fused multiply-add
+    # (c * invden is not rounded before the add); a float32 product is exact
+    # in double, so one double add rounded to float32 reproduces it
+    cseg = c.view(rows, W, S).double()
+    iseg = invden.view(W, S).double()
     seg_mass = torch.zeros(rows, W)
     for i in range(S):                                   # ascending = kernel
-        seg_mass = seg_mass + pseg[:, :, i]
+        seg_mass = (cseg[:, :, i] * iseg[:, i] + seg_mass.double()).float()
     total = _butterfly_sum64(seg_mass)
     qv = (p * (1.0 / total).unsqueeze(1)).contiguous()   # encoded density
     sscale = torch.where(seg_mass > 0, S / seg_mass,
@@ -728,6 +737,103 @@ def lda_apply_all(shard, word_rows, old_t, new_t, summary_row: int) -> None:
     srow = summary_row * K
     flat.scatter_add_(0, srow + o, -ones)
     flat.scatter_add_(0, srow + nw, ones)
+
+
+# K7d: packed per-segment tables for the wave sampler. rec[rows][64][4*S]
+# int32 holds {reserved[S] | prob[S] | qv[S] | alias[S]} per (word, lane
+# segment), S = K/64; top[rows][64][2] int32 holds {top_prob, top_alias}.
+# Float fields are stored as their bits. The counts stay in the dense
+# pulled snapshot (profiles/r04_lda_step.md: a count slot in the record,
+# refreshed every step, lost to it).
+LDA_PACKED_S = (1, 2, 4, 8)
+
+
+def lda_packed_supported(num_topics: int) -> bool:
+    return num_topics % 64 == 0 and num_topics // 64 in LDA_PACKED_S
+
+
+def lda_packed_alloc(rows: int, num_topics: int, device):
+    """Zeroed (rec, top) for `rows` words."""
+    assert lda_packed_supported(num_topics), num_topics
+    S = num_topics // 64
+    rec = torch.zeros(rows, 64, 4 * S, dtype=torch.int32, device=device)
+    top = torch.zeros(rows, 64, 2, dtype=torch.int32, device=device)
+    return rec, top
+
+
+def _rows32(src_rows):
+    if src_rows is None:
+        return None
+    return src_rows.to(torch.int32).contiguous()
+
+
+def lda_alias_build_packed(src: torch.Tensor, src_rows, topic_sum,
+                           beta: float, num_vocabs: int, rec: torch.Tensor,
+                           top: torch.Tensor):
+    """lda_alias_build over rows `src[src_rows]` (or `src[:rows]` when
+    src_rows is None; the former reads a table shard in place), written
+    into the packed tables. Stored values are bit-identical to
+    lda_alias_build's. Returns (invden, qsum)."""
+    if _use_hip(src):
+        return tuple(_hip.lda_alias_build_packed(
+            src, _rows32(src_rows), topic_sum.contiguous(), float(beta),
+            int(num_vocabs), rec, top))
+    rows, S = rec.shape[0], rec.shape[2] // 4
+    wt = src[src_rows.long()] if src_rows is not None else src[:rows]
+    prob, alias, tprob, talias, qv, qsum, invden = lda_alias_build(
+        wt, topic_sum, beta, num_vocabs)
+    r = rec.view(rows, 64, 4, S)
+    r[:, :, 1] = prob.view(torch.int32).view(rows, 64, S)
+    r[:, :, 2] = qv.view(torch.int32).view(rows, 64, S)
+    r[:, :, 3] = alias.view(rows, 64, S)
+    top[:, :, 0] = tprob.view(torch.int32)
+    top[:, :, 1] = talias
+    return invden, qsum
+
+
+def lda_unpack_tables(rec: torch.Tensor, top: torch.Tensor):
+    """The legacy arrays held by the packed tables:
+    (prob, alias, top_prob, top_alias, qv)."""
+    rows, S = rec.shape[0], rec.shape[2] // 4
+    K = 64 * S
+    r = rec.view(rows, 64, 4, S)
+
+    def field(i):
+        return r[:, :, i].reshape(rows, K).contiguous()
+
+    return (field(1).view(torch.float32), field(3),
+            top[:, :, 0].contiguous().view(torch.float32),
+            top[:, :, 1].contiguous(), field(2).view(torch.float32))
+
+
+def lda_mh_wave_packed(doc_topic: torch.Tensor, word_topic: torch.Tensor,
+                       rec: torch.Tensor, top: torch.Tensor,
+                       invden: torch.Tensor, doc_offsets: torch.Tensor,
+                       word_ids: torch.Tensor, assignments: torch.Tensor,
+                       alpha: float, beta: float, seed: int, shard=None,
+                       row_of_local=None,
+                       summary_row: int = -1) -> torch.Tensor:
+    """lda_mh_wave reading the packed tables (word_ids int32). With `shard`
+    the sweep also applies every changed token's -1/+1 to
+    shard[row_of_local[word]] and to shard[summary_row] (what lda_apply_all
+    does from an old/new copy of the assignments): it samples from the
+    snapshot word_topic, never from the shard, so the result is the same.
+    On CPU this is the serial sampler over the unpacked tables, as for
+    lda_mh_wave."""
+    if _use_hip(rec):
+        return _hip.lda_mh_wave_packed(
+            doc_topic, word_topic, rec, top, invden, doc_offsets, word_ids,
+            assignments, float(alpha), float(beta), int(seed), shard,
+            _rows32(row_of_local) if shard is not None else None,
+            int(summary_row))
+    prob, alias, tprob, talias, qv = lda_unpack_tables(rec, top)
+    old = assignments.clone() if shard is not None else None
+    lda_mh(doc_topic, word_topic, invden, prob, alias, tprob, talias, qv,
+           doc_offsets, word_ids.long(), assignments, alpha, beta, seed)
+    if shard is not None:
+        lda_apply_all(shard, row_of_local.long()[word_ids.long()], old,
+                      assignments, summary_row)
+    return assignments
 
 
 # ---------------------------------------------------------------------------

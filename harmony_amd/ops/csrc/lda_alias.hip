@@ -356,6 +356,300 @@ void lda_mh_wave_kernel(int* __restrict__ doc_topic,
     doc_topic[gbase + i] = ndw[i];
 }
 
+
+// K7d: packed tables for the wave sampler. The legacy layout keeps eight
+// [rows][K] / [rows][64] arrays and a token touches ~9 different 128-byte
+// lines of them. The stale tables of one (word, lane segment) pair live
+// here in ONE record of 16*S bytes (S = K/64 topics per segment):
+//   rec[row][seg] = { reserved[S] | prob[S] | qv[S] | alias[S] } (int32 bits)
+//   top[row][seg] = { top_prob, top_alias }                      (8 bytes)
+// t1 is drawn inside segment g, so prob/alias/qv[t1] are one record and
+// qv[s] is record s/S. The counts stay in the dense pulled snapshot: a
+// per-step refresh of a count slot inside every record (the reserved slot)
+// was measured and lost, see profiles/r04_lda_step.md. That leaves about
+// six lines per token: top, rec(g), rec(s/S) and count[s], count[t1],
+// count[t2].
+
+// S consecutive ints at a 4*S-byte aligned address, widest access <= 16 B
+template <int S>
+__device__ __forceinline__ void ld_slot(const int* __restrict__ p,
+                                        int (&v)[S]) {
+  if constexpr (S == 1) {
+    v[0] = p[0];
+  } else if constexpr (S == 2) {
+    const int2 t = *reinterpret_cast<const int2*>(p);
+    v[0] = t.x; v[1] = t.y;
+  } else {
+#pragma unroll
+    for (int i = 0; i < S / 4; ++i) {
+      const int4 t = reinterpret_cast<const int4*>(p)[i];
+      v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z;
+      v[4 * i + 3] = t.w;
+    }
+  }
+}
+
+template <int S>
+__device__ __forceinline__ void st_slot(int* __restrict__ p,
+                                        const int (&v)[S]) {
+  if constexpr (S == 1) {
+    p[0] = v[0];
+  } else if constexpr (S == 2) {
+    *reinterpret_cast<int2*>(p) = make_int2(v[0], v[1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < S / 4; ++i)
+      reinterpret_cast<int4*>(p)[i] =
+          make_int4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+  }
+}
+
+// One whole record in registers, fields picked by compare/select. Each
+// field is kept as its own 4-wide pieces: one 4*S-wide array indexed by a
+// lane-varying value is put in scratch memory by the compiler.
+__device__ __forceinline__ int sel4(const int4& v, int i) {
+  return (i == 0) ? v.x : (i == 1) ? v.y : (i == 2) ? v.z : v.w;
+}
+
+template <int S> struct SegRecord;
+
+template <> struct SegRecord<1> {
+  int4 t;
+  __device__ __forceinline__ explicit SegRecord(const int* p)
+      : t(*reinterpret_cast<const int4*>(p)) {}
+  __device__ __forceinline__ int field(int f, int) const { return sel4(t, f); }
+};
+
+template <> struct SegRecord<2> {
+  int4 a, b;                       // {c0 c1 p0 p1} {q0 q1 a0 a1}
+  __device__ __forceinline__ explicit SegRecord(const int* p)
+      : a(reinterpret_cast<const int4*>(p)[0]),
+        b(reinterpret_cast<const int4*>(p)[1]) {}
+  __device__ __forceinline__ int field(int f, int i) const {
+    return sel4(f < 2 ? a : b, (f & 1) * 2 + i);
+  }
+};
+
+template <> struct SegRecord<4> {
+  int4 t[4];
+  __device__ __forceinline__ explicit SegRecord(const int* p) {
+#pragma unroll
+    for (int f = 0; f < 4; ++f) t[f] = reinterpret_cast<const int4*>(p)[f];
+  }
+  __device__ __forceinline__ int field(int f, int i) const {
+    return sel4(t[f], i);
+  }
+};
+
+template <> struct SegRecord<8> {
+  int4 t[8];
+  __device__ __forceinline__ explicit SegRecord(const int* p) {
+#pragma unroll
+    for (int f = 0; f < 8; ++f) t[f] = reinterpret_cast<const int4*>(p)[f];
+  }
+  __device__ __forceinline__ int field(int f, int i) const {
+    const int lo = sel4(t[2 * f], i & 3), hi = sel4(t[2 * f + 1], i & 3);
+    return (i < 4) ? lo : hi;
+  }
+};
+
+// alias_build_kernel with the row read through src_rows (the table shard in
+// place) or densely, and the tables written as packed records. Same
+// arithmetic in the same order: the stored bits equal alias_build_kernel's.
+template <int S>
+__global__ void alias_build_packed_kernel(const int* __restrict__ src,
+                                          const int* __restrict__ src_rows,
+                                          const float* __restrict__ invden,
+                                          float beta,
+                                          int* __restrict__ rec,   // [rows][64][4S]
+                                          int2* __restrict__ top,  // [rows][64]
+                                          float* __restrict__ qsum,
+                                          int rows) {
+  constexpr int K = S * WAVE;
+  extern __shared__ float smem_f[];
+  const int wave = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  constexpr size_t per_wave = 3 * (size_t)K + 3 * WAVE;
+  float* pr = smem_f + (size_t)wave * per_wave;
+  int* al = (int*)(pr + K);
+  int* lk = al + K;
+  float* tp = (float*)(lk + K);
+  int* ta = (int*)(tp + WAVE);
+  int* tl = ta + WAVE;
+  const int waves_wg = blockDim.x / WAVE;
+  for (int row = blockIdx.x * waves_wg + wave; row < rows;
+       row += gridDim.x * waves_wg) {
+    const int64_t base = (int64_t)(src_rows ? src_rows[row] : row) * K;
+    int cnt[S];
+    ld_slot<S>(src + base + lane * S, cnt);
+    float seg_mass = 0.f;
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+      const int k = lane * S + i;
+      const float c = (float)cnt[i] + beta;
+      pr[k] = c * invden[k];
+      // alias_build_kernel's `seg_mass += p` is contracted by the compiler
+      // into a fused multiply-add (p itself is stored rounded); written
+      // out here so that unrolling cannot decide otherwise
+      seg_mass = __fmaf_rn(c, invden[k], seg_mass);
+    }
+    const float total = wave_reduce_sum(seg_mass);
+    const float inv_total = 1.f / total;
+    int out[S];
+    int* r = rec + ((int64_t)row * WAVE + lane) * (4 * S);
+#pragma unroll
+    for (int i = 0; i < S; ++i)
+      out[i] = __float_as_int(pr[lane * S + i] * inv_total);
+    st_slot<S>(r + 2 * S, out);                         // qv
+    const float sscale = (seg_mass > 0.f) ? (float)S / seg_mass : 0.f;
+#pragma unroll
+    for (int i = 0; i < S; ++i) pr[lane * S + i] *= sscale;
+    vose_serial(pr + lane * S, al + lane * S, lk + lane * S, S);
+    tp[lane] = seg_mass * (float)WAVE / total;
+    if (lane == 0) {
+      vose_serial(tp, ta, tl, WAVE);
+      qsum[row] = total;
+    }
+    // lanes 1..63 read what lane 0 just wrote to tp/ta: without the fence
+    // the compiler forwards each lane's own earlier store of tp[lane]
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int i = 0; i < S; ++i) out[i] = __float_as_int(pr[lane * S + i]);
+    st_slot<S>(r + S, out);                             // prob
+#pragma unroll
+    for (int i = 0; i < S; ++i) out[i] = al[lane * S + i];
+    st_slot<S>(r + 3 * S, out);                         // alias
+    top[(int64_t)row * WAVE + lane] =
+        make_int2(__float_as_int(tp[lane]), ta[lane]);
+  }
+}
+
+// lda_mh_wave_kernel reading the packed tables. Every float expression and
+// RNG counter is the legacy kernel's, so with the same LDS interleaving the
+// samples are bit-identical. rec(g) is loaded whole (S x 16 bytes) and
+// prob[eb]/alias[eb], then qv[t1], are selected in registers.
+// FUSED: the kernel holds (word, old topic, new topic) of every token and
+// samples from the pulled snapshot, never from the shard, so it applies the
+// +/-1 to the shard row itself; the scattered atomics overlap the sampler's
+// own load latency instead of running as a pass of their own. Summary-row
+// deltas stage through an LDS histogram per workgroup (see
+// lda_apply_all_kernel for why not per-token global atomics).
+template <int S, bool FUSED>
+__global__ __launch_bounds__(256)
+void lda_mh_wave_packed_kernel(int* __restrict__ doc_topic,
+                               const int* __restrict__ word_topic,
+                               const int* __restrict__ rec,
+                               const int2* __restrict__ top,
+                               const float* __restrict__ invden,
+                               const int64_t* __restrict__ doc_offsets,
+                               const int* __restrict__ word_ids,
+                               int* __restrict__ z,
+                               int* __restrict__ shard,
+                               const int* __restrict__ row_of_local,
+                               int64_t summary_row,
+                               float alpha, float beta,
+                               int n_docs, unsigned int seed) {
+  constexpr int K = S * WAVE;
+  constexpr int R = 4 * S;                     // ints per record
+  extern __shared__ int ndw[];                 // [waves_wg][K] (+ [K] FUSED)
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int waves_wg = blockDim.x >> 6;
+  const int doc = blockIdx.x * waves_wg + wave;
+  int* nd = ndw + (size_t)wave * K;
+  int* ssum = ndw + (size_t)waves_wg * K;
+  const int64_t gbase = (int64_t)blockIdx.x * waves_wg * K;
+  const int ndocs_wg = min(waves_wg, n_docs - blockIdx.x * waves_wg);
+  for (int i = tid; i < ndocs_wg * K; i += blockDim.x)
+    ndw[i] = doc_topic[gbase + i];
+  if (FUSED)
+    for (int k = tid; k < K; k += blockDim.x) ssum[k] = 0;
+  __syncthreads();
+  const bool active = doc < n_docs;
+  const int64_t p0 = active ? doc_offsets[doc] : 0;
+  const int64_t p1 = active ? doc_offsets[doc + 1] : 0;
+  const float Ld = (float)(p1 - p0);
+  const float aK = alpha * (float)K;
+  const float p_uniform = aK / (aK + Ld);
+  for (int64_t p = p0 + lane; p < p1; p += WAVE) {
+    const int w = word_ids[p];
+    const int* __restrict__ wrec = rec + (int64_t)w * (WAVE * R);
+    int s = z[p];
+    const int s_old = s;
+    const int* __restrict__ wcnt = word_topic + (int64_t)w * K;
+    int cnt_s = wcnt[s];
+    const float qv_s =
+        __int_as_float(wrec[(s / S) * R + 2 * S + (s % S)]);
+    const int nds0 = atomicAdd(&nd[s], -1) - 1;
+    const unsigned int c0 = (unsigned int)(p * 8);
+    // ---- word proposal (two-level alias) ----
+    {
+      const float u1 = rng_uniform(seed, c0 + 0) * (float)WAVE;
+      int gb = (int)u1;
+      if (gb >= WAVE) gb = WAVE - 1;
+      const int2 tpa = top[(int64_t)w * WAVE + gb];
+      const int g = (u1 - (float)gb < __int_as_float(tpa.x)) ? gb : tpa.y;
+      const float u2 = rng_uniform(seed, c0 + 6) * (float)S;
+      int eb = (int)u2;
+      if (eb >= S) eb = S - 1;
+      const SegRecord<S> rg(wrec + g * R);     // whole record, S x 16 B
+      const int lt = (u2 - (float)eb < __int_as_float(rg.field(1, eb)))
+                         ? eb : rg.field(3, eb);
+      const int t1 = g * S + lt;
+      const int cnt_t = wcnt[t1];
+      const float qv_t = __int_as_float(rg.field(2, lt));
+      const float pi_s = ((float)nds0 + alpha) *
+          ((float)cnt_s + beta) * invden[s];
+      const float pi_t = ((float)nd[t1] + alpha) *
+          ((float)cnt_t + beta) * invden[t1];
+      const float a1 = (pi_t * qv_s) / (pi_s * qv_t);
+      if (rng_uniform(seed, c0 + 1) < a1) { s = t1; cnt_s = cnt_t; }
+    }
+    // ---- doc proposal ----
+    {
+      int t2;
+      if (rng_uniform(seed, c0 + 2) < p_uniform) {
+        t2 = (int)(rng_uniform(seed, c0 + 3) * (float)K);
+        if (t2 >= K) t2 = K - 1;
+      } else {
+        int64_t j = p0 + (int64_t)(rng_uniform(seed, c0 + 4) * Ld);
+        if (j >= p1) j = p1 - 1;
+        t2 = (j == p) ? s : z[j];
+      }
+      const int cnt_t2 = wcnt[t2];
+      const float nds = (float)nd[s], ndt = (float)nd[t2];
+      const float qs = nds + 1.f + alpha;
+      const float qt = ndt + (t2 == s ? 1.f : 0.f) + alpha;
+      const float pis = (nds + alpha) *
+          ((float)cnt_s + beta) * invden[s];
+      const float pit = (ndt + alpha) *
+          ((float)cnt_t2 + beta) * invden[t2];
+      const float a2 = (pit * qs) / (pis * qt);
+      if (rng_uniform(seed, c0 + 5) < a2) s = t2;
+    }
+    atomicAdd(&nd[s], 1);
+    z[p] = s;
+    if (FUSED && s != s_old) {
+      int* srow = shard + (int64_t)row_of_local[w] * K;
+      atomicSub(&srow[s_old], 1);
+      atomicAdd(&srow[s], 1);
+      atomicSub(&ssum[s_old], 1);
+      atomicAdd(&ssum[s], 1);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < ndocs_wg * K; i += blockDim.x)
+    doc_topic[gbase + i] = ndw[i];
+  if (FUSED)
+    for (int k = tid; k < K; k += blockDim.x) {
+      const int v = ssum[k];
+      if (v != 0) atomicAdd(&shard[summary_row * K + k], v);
+    }
+}
+
 }  // namespace
 
 std::vector<torch::Tensor> lda_alias_build(torch::Tensor word_topic,
@@ -458,5 +752,130 @@ torch::Tensor lda_mh_wave(torch::Tensor doc_topic, torch::Tensor word_topic,
                      assignments.data_ptr<int>(),
                      (float)alpha, (float)beta, D, K,
                      (unsigned int)(seed & 0xffffffff));
+  return assignments;
+}
+
+// ---- K7d host entries: packed tables ----
+
+#define LDA_DISPATCH_S(S_, ...)                                     \
+  switch (S_) {                                                     \
+    case 1: { constexpr int S = 1; __VA_ARGS__; break; }            \
+    case 2: { constexpr int S = 2; __VA_ARGS__; break; }            \
+    case 4: { constexpr int S = 4; __VA_ARGS__; break; }            \
+    case 8: { constexpr int S = 8; __VA_ARGS__; break; }            \
+    default: TORCH_CHECK(false, "packed LDA tables need K/64 in {1,2,4,8}"); \
+  }
+
+static int packed_S(const torch::Tensor& rec, const torch::Tensor& top) {
+  CHECK_IN(rec); CHECK_IN(top);
+  TORCH_CHECK(rec.dtype() == torch::kInt32 && top.dtype() == torch::kInt32);
+  TORCH_CHECK(rec.dim() == 3 && rec.size(1) == WAVE && rec.size(2) % 4 == 0,
+              "rec must be [rows][64][4*S] int32");
+  TORCH_CHECK(top.dim() == 3 && top.size(0) == rec.size(0) &&
+              top.size(1) == WAVE && top.size(2) == 2,
+              "top must be [rows][64][2] int32");
+  return (int)(rec.size(2) / 4);
+}
+
+static const int* check_rows(const c10::optional<torch::Tensor>& src_rows,
+                             const torch::Tensor& src, int64_t rows, int K) {
+  CHECK_IN(src);
+  TORCH_CHECK(src.dtype() == torch::kInt32 && src.dim() == 2 &&
+              src.size(1) == K, "src must be [n][K] int32");
+  if (!src_rows.has_value()) {
+    TORCH_CHECK(src.size(0) >= rows, "src has fewer rows than rec");
+    return nullptr;
+  }
+  const torch::Tensor& r = *src_rows;
+  CHECK_IN(r);
+  TORCH_CHECK(r.dtype() == torch::kInt32 && r.dim() == 1 &&
+              r.size(0) == rows, "src_rows must be [rows] int32");
+  return r.data_ptr<int>();
+}
+
+std::vector<torch::Tensor> lda_alias_build_packed(
+    torch::Tensor src, c10::optional<torch::Tensor> src_rows,
+    torch::Tensor topic_sum, double beta, int64_t num_vocabs,
+    torch::Tensor rec, torch::Tensor top) {
+  CHECK_IN(topic_sum);
+  const int S_ = packed_S(rec, top);
+  const int rows = rec.size(0), K = S_ * WAVE;
+  TORCH_CHECK(topic_sum.numel() == K);
+  const int* rows_p = check_rows(src_rows, src, rows, K);
+  auto invden = 1.0 / (topic_sum.to(torch::kFloat32)
+                       + (double)num_vocabs * beta);
+  invden = invden.contiguous();
+  auto qsum = torch::empty({rows}, invden.options());
+  if (rows > 0) {
+    const int waves = BUILD_WAVES;
+    dim3 blk(WAVE * waves);
+    dim3 grid(std::min((rows + waves - 1) / waves, 8192));
+    const size_t shmem = (size_t)waves * (3 * K + 3 * WAVE) * 4;
+    LDA_DISPATCH_S(S_, hipLaunchKernelGGL(
+        alias_build_packed_kernel<S>, grid, blk, shmem, current_stream(),
+        src.data_ptr<int>(), rows_p, invden.data_ptr<float>(), (float)beta,
+        rec.data_ptr<int>(), reinterpret_cast<int2*>(top.data_ptr<int>()),
+        qsum.data_ptr<float>(), rows));
+  }
+  return {invden, qsum};
+}
+
+torch::Tensor lda_mh_wave_packed(torch::Tensor doc_topic,
+                                 torch::Tensor word_topic, torch::Tensor rec,
+                                 torch::Tensor top, torch::Tensor invden,
+                                 torch::Tensor doc_offsets,
+                                 torch::Tensor word_ids,
+                                 torch::Tensor assignments,
+                                 double alpha, double beta, int64_t seed,
+                                 c10::optional<torch::Tensor> shard,
+                                 c10::optional<torch::Tensor> row_of_local,
+                                 int64_t summary_row) {
+  CHECK_IN(doc_topic); CHECK_IN(word_topic); CHECK_IN(invden); CHECK_IN(doc_offsets);
+  CHECK_IN(word_ids); CHECK_IN(assignments);
+  const int S_ = packed_S(rec, top);
+  const int D = doc_topic.size(0), K = doc_topic.size(1);
+  TORCH_CHECK(K == S_ * WAVE, "doc_topic width does not match rec");
+  TORCH_CHECK(doc_topic.dtype() == torch::kInt32 &&
+              assignments.dtype() == torch::kInt32 &&
+              word_ids.dtype() == torch::kInt32 &&
+              doc_offsets.dtype() == torch::kInt64 &&
+              invden.dtype() == torch::kFloat32 && invden.numel() == K);
+  TORCH_CHECK(doc_offsets.numel() == D + 1 &&
+              word_ids.numel() == assignments.numel());
+  const bool fused = shard.has_value();
+  int* shard_p = nullptr; const int* rol_p = nullptr;
+  if (fused) {
+    TORCH_CHECK(row_of_local.has_value(), "fused apply needs row_of_local");
+    CHECK_IN(*shard); CHECK_IN(*row_of_local);
+    TORCH_CHECK(shard->dtype() == torch::kInt32 && shard->dim() == 2 &&
+                shard->size(1) == K);
+    TORCH_CHECK(row_of_local->dtype() == torch::kInt32 &&
+                row_of_local->numel() == rec.size(0));
+    TORCH_CHECK(summary_row >= 0 && summary_row < shard->size(0));
+    shard_p = shard->data_ptr<int>();
+    rol_p = row_of_local->data_ptr<int>();
+  }
+  TORCH_CHECK(word_topic.dtype() == torch::kInt32 &&
+              word_topic.dim() == 2 && word_topic.size(1) == K &&
+              word_topic.size(0) >= rec.size(0),
+              "word_topic must be [>= rec rows][K] int32");
+  if (D == 0) return assignments;
+  const int waves_wg = 4;              // 256 threads, 4 docs per block
+  dim3 blk(WAVE * waves_wg), grid((D + waves_wg - 1) / waves_wg);
+  const size_t shmem = ((size_t)waves_wg + (fused ? 1 : 0)) * K * 4;
+#define LDA_LAUNCH_PACKED(F)                                              \
+  hipLaunchKernelGGL((lda_mh_wave_packed_kernel<S, F>), grid, blk, shmem, \
+                     current_stream(), doc_topic.data_ptr<int>(),         \
+                     word_topic.data_ptr<int>(), rec.data_ptr<int>(),     \
+                     reinterpret_cast<const int2*>(top.data_ptr<int>()),  \
+                     invden.data_ptr<float>(),                            \
+                     doc_offsets.data_ptr<int64_t>(),                     \
+                     word_ids.data_ptr<int>(),                            \
+                     assignments.data_ptr<int>(), shard_p, rol_p,         \
+                     summary_row, (float)alpha, (float)beta, D,           \
+                     (unsigned int)(seed & 0xffffffff))
+  LDA_DISPATCH_S(S_, if (fused) LDA_LAUNCH_PACKED(true);
+                     else LDA_LAUNCH_PACKED(false));
+#undef LDA_LAUNCH_PACKED
   return assignments;
 }

@@ -61,6 +61,20 @@ torch::Tensor lda_mh(torch::Tensor doc_topic, torch::Tensor word_topic,
                      torch::Tensor doc_offsets,
                      torch::Tensor word_ids, torch::Tensor assignments,
                      double alpha, double beta, int64_t seed);
+std::vector<torch::Tensor> lda_alias_build_packed(
+    torch::Tensor src, c10::optional<torch::Tensor> src_rows,
+    torch::Tensor topic_sum, double beta, int64_t num_vocabs,
+    torch::Tensor rec, torch::Tensor top);
+torch::Tensor lda_mh_wave_packed(torch::Tensor doc_topic,
+                                 torch::Tensor word_topic, torch::Tensor rec,
+                                 torch::Tensor top, torch::Tensor invden,
+                                 torch::Tensor doc_offsets,
+                                 torch::Tensor word_ids,
+                                 torch::Tensor assignments,
+                                 double alpha, double beta, int64_t seed,
+                                 c10::optional<torch::Tensor> shard,
+                                 c10::optional<torch::Tensor> row_of_local,
+                                 int64_t summary_row);
 void lasso_cd(torch::Tensor Xt, torch::Tensor r, torch::Tensor w,
               torch::Tensor col_sq, double lam_n);
 torch::Tensor os_shard_alloc(int64_t rows, int64_t k, int64_t dtype_i32);
@@ -138,6 +152,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Metropolis-Hastings alias LDA sweep, thread-per-doc (K7b)");
   m.def("lda_mh_wave", &lda_mh_wave,
         "wave-per-doc MH sweep (K7c, approximate within-doc parallelism)");
+  m.def("lda_alias_build_packed", &lda_alias_build_packed,
+        "alias tables as packed per-segment records (K7d)");
+  m.def("lda_mh_wave_packed", &lda_mh_wave_packed,
+        "wave-per-doc MH sweep over packed tables, optional fused apply (K7d)");
   m.def("gbt_hist", &gbt_hist, "GBT level histogram build (K10)");
   m.def("lasso_cd", &lasso_cd, "Lasso persistent CD sweep (K11)");
   m.def("os_shard_alloc", &os_shard_alloc, "one-sided shard (hipMalloc)");
