@@ -12,7 +12,23 @@ coordinate step is two rocBLAS dot/axpy column ops on the device-resident
 batch; the full sweep stays on the GPU (F small relative to batch).
 
 App args: num_features, num_parts, batch_size, lam, step_size(unused),
-noise.
+noise, density; sparse (default false) and nnz_per_row (synthetic sparse
+generator, default 32).
+
+sparse=true keeps every batch as a SparseBatch (CSR + static column index),
+as the reference does (LassoETParser createSparse, horzcatVecSparse at
+LassoTrainer.java:273-283), and runs the K11s sweep (ops/csrc/
+lasso_sparse.hip) over the features PRESENT in the batch: memory and time
+follow the non-zeros, not B * F, so num_features may be far wider than a row
+is long. Pull and push stay dense ([P, F/P]).
+
+The two paths differ on purpose in one place. The sparse sweep skips a
+feature that has no entries in the batch (or whose column mass is <= 1e-9)
+and keeps its weight, as the reference does (LassoTrainer.java:199-208,
+`continue`). The dense sweep visits every feature: an all-zero column has
+c = w * 1e-9 after the clamp of col_sq, so the soft-threshold drives that
+weight to 0. On data where every column is present in every batch the two
+compute the same thing up to fp32 summation order.
 """
 
 from __future__ import annotations
@@ -24,6 +40,7 @@ from harmony_amd.dolphin.data_provider import TrainingDataProvider
 from harmony_amd.dolphin.model_accessor import ETModelAccessor
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
 from harmony_amd.et.table import Table
+from harmony_amd.mlapps.sparse_batch import SparseBatch
 from harmony_amd.utils import stable_seed
 from harmony_amd import ops
 
@@ -33,9 +50,13 @@ ZERO_THRESHOLD = 1e-9
 
 def defaults(job: JobConfig) -> dict:
     a = dict(num_features=256, num_parts=16, batch_size=2048, lam=0.05,
-             noise=0.1, density=0.25)
+             noise=0.1, density=0.25, sparse="false", nnz_per_row=32)
     a.update(job.app_args)
     return a
+
+
+def _is_sparse(a: dict) -> bool:
+    return str(a.get("sparse", "")).lower() in ("true", "1")
 
 
 def model_table_cfg(job: JobConfig, world_size: int) -> TableConfig:
@@ -57,6 +78,8 @@ def make_batches(job: JobConfig, rank: int, device: torch.device,
                  world_size: int = 1):
     a = defaults(job)
     F = a["num_features"]
+    if _is_sparse(a):
+        return _make_sparse_batches(job, a, rank, device, world_size)
     if job.app_args.get("input"):
         # sample_lasso rows "label idx:val ..." (reference LassoParser)
         from harmony_amd import dataloader as dl
@@ -78,6 +101,73 @@ def make_batches(job: JobConfig, rank: int, device: torch.device,
         y = X @ w_true + a["noise"] * torch.randn(a["batch_size"], generator=g)
         blocks.append((X.to(device), y.to(device)))
     return blocks, w_true
+
+
+def _make_sparse_batches(job: JobConfig, a: dict, rank: int,
+                         device: torch.device, world_size: int):
+    """make_batches for sparse=true: the same block structure as the dense
+    branch, every block a (SparseBatch, y) pair. No tensor with B*F elements
+    is built on either path."""
+    F = int(a["num_features"])
+    if a.get("input"):
+        from harmony_amd import dataloader as dl
+
+        row_ptr, col, val, y = dl.parse_libsvm_csr_split(
+            a["input"], rank, world_size, F)
+        n_blocks = max(1, job.num_worker_blocks or job.num_mini_batches)
+        n = y.shape[0]
+        # torch.chunk's row ranges, so block i holds the rows the dense
+        # branch would give it
+        size = -(-n // n_blocks) if n else 0
+        blocks = []
+        for lo in range(0, max(1, n), max(1, size)):
+            hi = min(n, lo + size)
+            e0, e1 = int(row_ptr[lo]), int(row_ptr[hi])
+            x = SparseBatch(row_ptr[lo:hi + 1] - e0, col[e0:e1],
+                            val[e0:e1], F)
+            blocks.append((x.to(device), y[lo:hi].to(device)))
+        return blocks, None
+    B = int(a["batch_size"])
+    k = max(1, min(int(a["nnz_per_row"]), F))
+    g = torch.Generator().manual_seed(stable_seed(job.job_id, "data", rank))
+    w_true = torch.randn(F, generator=g)
+    mask = torch.rand(F, generator=g) < a["density"]
+    w_true = w_true * mask
+    blocks = []
+    n_blocks = job.num_worker_blocks or job.num_mini_batches
+    for _ in range(n_blocks):
+        # per-row random feature subset: k draws, sorted, repeats dropped
+        cols = torch.randint(0, F, (B, k), generator=g).sort(dim=1).values
+        keep = torch.ones((B, k), dtype=torch.bool)
+        keep[:, 1:] = cols[:, 1:] != cols[:, :-1]
+        vals = torch.randn(B, k, generator=g) * keep
+        y = (vals * w_true[cols]).sum(dim=1) \
+            + a["noise"] * torch.randn(B, generator=g)
+        row_ptr = torch.zeros(B + 1, dtype=torch.int64)
+        row_ptr[1:] = torch.cumsum(keep.sum(dim=1), 0)
+        x = SparseBatch(row_ptr, cols[keep].to(torch.int32), vals[keep], F)
+        blocks.append((x.to(device), y.to(device)))
+    return blocks, w_true
+
+
+def _sparse_col_sq(X: SparseBatch) -> torch.Tensor:
+    """Per-present-feature sum of squares, clamped as the dense path's;
+    computed once and kept on the batch (a block is static, and prefix()
+    builds a new batch, so the cache cannot go stale)."""
+    col_sq = getattr(X, "_harmony_colsq", None)
+    if col_sq is None:
+        nf = X.feat_ids.shape[0]
+        seg = torch.repeat_interleave(
+            torch.arange(nf, device=X.device),
+            X.feat_ptr[1:] - X.feat_ptr[:-1])
+        # summed in fp64 and rounded once: the device index_add_ is atomic,
+        # and its order must not show in the fp32 value
+        v = X.feat_val.double()
+        col_sq = torch.zeros(nf, dtype=torch.float64, device=X.device)
+        col_sq.index_add_(0, seg, v * v)
+        col_sq = col_sq.float().clamp_min(ZERO_THRESHOLD)
+        X._harmony_colsq = col_sq
+    return col_sq
 
 
 class LassoTrainer(Trainer):
@@ -107,6 +197,15 @@ class LassoTrainer(Trainer):
             return
         F = X.shape[1]
         lam_n = self.a["lam"] * X.shape[0]
+        if isinstance(X, SparseBatch):
+            # one K11s sweep over the batch's present features; the
+            # residual is built inside the op
+            w, r = ops.lasso_cd_sparse(X.feat_ids, X.feat_ptr, X.feat_row,
+                                       X.feat_val, y, self.w,
+                                       _sparse_col_sq(X), lam_n)
+            self.delta = w - self.w
+            self._loss = (r * r).mean()
+            return
         r = y - X @ self.w                     # residual
         col_sq = getattr(X, "_harmony_colsq", None)
         if col_sq is None:
@@ -153,6 +252,8 @@ def build(job: JobConfig, ctx, cp):
         # frac<=0 -> EMPTY batch: a stopped worker (StopWorkerOp) does
         # zero work and its sparse pulls/pushes carry zero keys
         n = 0 if frac <= 0 else max(1, int(b[0].shape[0] * frac))
+        if isinstance(b[0], SparseBatch):
+            return (b[0].prefix(n), b[1][:n])
         return (b[0][:n], b[1][:n])
 
     provider = TrainingDataProvider(reslice=_reslice, local_blocks=blocks)

@@ -15,6 +15,8 @@ Kernel inventory (reference hot loops):
   K4s mlr_sparse_fwd/grad MLRTrainer.java:374-398 over SparseVector rows
   K7  lda_gibbs           SparseLDASampler.java:141-274
   K9  scatter-apply       LDAETModelUpdateFunction.java:43-64
+  K11 lasso_cd            LassoTrainer.java:164-190
+  K11s lasso_cd_sparse    LassoTrainer.java:164-208 over SparseVector columns
   K12 loss reductions     NMFTrainer.java:414-456 etc.
   K13 pregel_pull         pregel MessageManager.addMessage + MessageCombiner
 """
@@ -896,6 +898,95 @@ def lasso_cd(X: torch.Tensor, r: torch.Tensor, w: torch.Tensor,
               / col_sq[i])
         r = r + xi * (w[i] - wn)
         w[i] = wn
+    return w, r
+
+
+# ---------------------------------------------------------------------------
+# K11s: Lasso CD sweep over a sparse batch's column index
+# ---------------------------------------------------------------------------
+
+LASSO_ZERO_THRESHOLD = 1e-9
+# rows K11s keeps in LDS (64 KiB less its scratch; the binding checks it)
+LASSO_SPARSE_MAX_ROWS = 16384 - 176
+
+
+def lasso_sparse_threads(nf: int, nnz: int) -> int:
+    """Threads of the one K11s workgroup, from the mean column length
+    nnz / nf: 64 up to a mean of 64 entries, 256 up to 512, else 1024.
+    One wave has no cross-wave partials and no hardware barrier per
+    coordinate, which is what a column of a few entries pays for; wider
+    workgroups win only once a column is long enough to amortise them
+    (measured against forced thread counts: profiles/lasso_sparse_ab.md).
+    A function of the batch alone, so a batch always runs with the same
+    summation order."""
+    mean = nnz / max(1, nf)
+    if mean <= 64:
+        return 64
+    if mean <= 512:
+        return 256
+    return 1024
+
+
+def lasso_cd_sparse(feat_ids: torch.Tensor, feat_ptr: torch.Tensor,
+                    feat_row: torch.Tensor, feat_val: torch.Tensor,
+                    y: torch.Tensor, w: torch.Tensor, col_sq: torch.Tensor,
+                    lam_n: float, _force_threads: int = 0
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One full cyclic coordinate-descent sweep over the features PRESENT in
+    a sparse batch (K11s, ops/csrc/lasso_sparse.hip; reference
+    LassoTrainer.java:164-208 over SparseVector columns). The batch is given
+    by its column index (SparseBatch): feat_ids int32 [nf] ascending,
+    feat_ptr int64 [nf+1], feat_row int32 [nnz] (each row at most once per
+    feature), feat_val float32 [nnz]; y [B], w [F], col_sq [nf] the
+    per-present-feature sum of squares.
+
+    r = y, then r[row] -= val * w for each present feature with w != 0, in
+    feature order. Then for each present feature k in order, f = feat_ids[k]:
+        c  = sum_e val[e] * r[row[e]] + w[f] * col_sq[k]
+        wn = sign(c) * max(|c| - lam_n, 0) / col_sq[k]
+        r[row[e]] += val[e] * (w[f] - wn);  w[f] = wn
+    A feature with no entries, or with col_sq[k] <= 1e-9, is skipped and
+    keeps its weight (upstream: `continue`), as does every feature absent
+    from the batch. Returns (w_new, r_new) with r_new = y - X w_new; inputs
+    are not mutated.
+
+    CPU tensors, HARMONY_FORCE_TORCH_OPS=1 and batches above
+    LASSO_SPARSE_MAX_ROWS take the torch loop below, which is the reference
+    implementation. _force_threads overrides lasso_sparse_threads (tests)."""
+    B, nf = y.shape[0], feat_ids.shape[0]
+    w = w.clone()
+    if B == 0 or nf == 0:
+        return w, y.clone()
+    if _use_hip(y) and B <= LASSO_SPARSE_MAX_ROWS:
+        threads = _force_threads or lasso_sparse_threads(
+            nf, feat_row.shape[0])
+        r = torch.empty_like(y)
+        _hip.lasso_cd_sparse(
+            feat_ids.contiguous(), feat_ptr.contiguous(),
+            feat_row.contiguous(), feat_val.contiguous(), y.contiguous(), w,
+            col_sq.contiguous(), float(lam_n), r, int(threads))
+        return w, r
+    r = y.clone()
+    ids = feat_ids.tolist()
+    ptr = feat_ptr.tolist()
+    rows = feat_row.long()
+    live = (w[feat_ids.long()] != 0).tolist()
+    for k, f in enumerate(ids):
+        if live[k] and ptr[k + 1] > ptr[k]:
+            sl = slice(ptr[k], ptr[k + 1])
+            r[rows[sl]] -= feat_val[sl] * w[f]
+    ok = ((col_sq > LASSO_ZERO_THRESHOLD)
+          & (feat_ptr[1:] > feat_ptr[:-1])).tolist()
+    for k, f in enumerate(ids):
+        if not ok[k]:
+            continue
+        sl = slice(ptr[k], ptr[k + 1])
+        rw, v = rows[sl], feat_val[sl]
+        c = v @ r[rw] + w[f] * col_sq[k]
+        wn = (torch.clamp(c.abs() - lam_n, min=0.0) * torch.sign(c)
+              / col_sq[k])
+        r[rw] += v * (w[f] - wn)
+        w[f] = wn
     return w, r
 
 

@@ -77,6 +77,11 @@ torch::Tensor lda_mh_wave_packed(torch::Tensor doc_topic,
                                  int64_t summary_row);
 void lasso_cd(torch::Tensor Xt, torch::Tensor r, torch::Tensor w,
               torch::Tensor col_sq, double lam_n);
+int64_t lasso_cd_sparse_max_rows();
+void lasso_cd_sparse(torch::Tensor feat_ids, torch::Tensor feat_ptr,
+                     torch::Tensor feat_row, torch::Tensor feat_val,
+                     torch::Tensor y, torch::Tensor w, torch::Tensor col_sq,
+                     double lam_n, torch::Tensor r_out, int64_t threads);
 torch::Tensor os_shard_alloc(int64_t rows, int64_t k, int64_t dtype_i32);
 torch::Tensor os_ipc_handle(torch::Tensor shard);
 int64_t os_ipc_open(torch::Tensor handle_bytes);
@@ -158,6 +163,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "wave-per-doc MH sweep over packed tables, optional fused apply (K7d)");
   m.def("gbt_hist", &gbt_hist, "GBT level histogram build (K10)");
   m.def("lasso_cd", &lasso_cd, "Lasso persistent CD sweep (K11)");
+  m.def("lasso_cd_sparse", &lasso_cd_sparse,
+        "Lasso CD sweep over a batch's column index (K11s)");
+  m.def("lasso_cd_sparse_max_rows", &lasso_cd_sparse_max_rows,
+        "largest batch K11s keeps in LDS");
   m.def("os_shard_alloc", &os_shard_alloc, "one-sided shard (hipMalloc)");
   m.def("os_ipc_handle", &os_ipc_handle, "export shard via hipIpc");
   m.def("os_ipc_open", &os_ipc_open, "map a peer shard (xGMI)");
