@@ -21,12 +21,21 @@ App args: num_features, batch_size, num_bins, max_depth, step_size
 (shrinkage), lam (leaf L2), objective ("regression" | "multiclass"
 with num_classes — one forest per label in the object table, reference
 GBTTrainer's valueTypeNum > 3 path / GroupedTree).
+
+Feature types (feature_types): with `input`, the metadata file (`metadata`,
+default <input>.meta) marks a feature continuous (0) or categorical (its
+number of categories); synthetic data makes its last `num_categorical`
+features categorical with `num_categories` values each. A categorical
+column is not binned (bin = category id, so at most min(num_bins, 64)
+categories) and is split by a SUBSET of its categories (K10b, reference
+bestSplitLabelFeature), stored per node as a 64-bit mask. Without a
+categorical feature nothing changes.
 """
 
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -43,7 +52,7 @@ MODEL_TABLE = "gbt_model"
 def defaults(job: JobConfig) -> dict:
     a = dict(num_features=32, batch_size=4096, num_bins=64, max_depth=4,
              step_size=0.1, lam=1.0, noise=0.1, objective="regression",
-             num_classes=3)
+             num_classes=3, num_categorical=0, num_categories=8)
     a.update(job.app_args)
     return a
 
@@ -51,12 +60,18 @@ def defaults(job: JobConfig) -> dict:
 @dataclass
 class GBTree:
     """Flat complete binary tree of depth d: internal nodes 0..2^d-2 hold
-    (feature, bin_threshold); leaves hold values. go left iff bin <= thr."""
+    (feature, bin_threshold); leaves hold values. Node kinds by threshold t:
+    t >= 0 continuous, right iff bin > t; t == -1 pass-through, always left;
+    t == -2 categorical, right iff bit `bin` of cat_mask[node] is set (a
+    category outside the mask, seen while building or not, goes left).
+    cat_mask is None for a tree built without feature types; the class-level
+    default also serves trees pickled before the field existed."""
 
     depth: int
     feature: List[int]          # [2^d - 1]
-    threshold: List[int]        # [2^d - 1] (bin index; -1 = pass-through)
+    threshold: List[int]        # [2^d - 1] (bin index; -1, -2: see above)
     leaf_value: List[float]     # [2^d]
+    cat_mask: Optional[List[int]] = None   # [2^d - 1] signed 64-bit masks
 
     def predict_bins(self, bins: torch.Tensor) -> torch.Tensor:
         """bins: [B, F] int64 quantized features -> [B] predictions."""
@@ -64,14 +79,30 @@ class GBTree:
         node = torch.zeros(B, dtype=torch.int64, device=bins.device)
         feat = torch.tensor(self.feature, device=bins.device)
         thr = torch.tensor(self.threshold, device=bins.device)
+        cm = None
+        if self.cat_mask is not None:
+            cm = torch.tensor(self.cat_mask, dtype=torch.int64,
+                              device=bins.device)
         for _ in range(self.depth):
             f = feat[node]
             t = thr[node]
-            go_right = (bins.gather(1, f.unsqueeze(1)).squeeze(1) > t) & (t >= 0)
+            b = bins.gather(1, f.unsqueeze(1)).squeeze(1)
+            if cm is None:
+                go_right = (b > t) & (t >= 0)
+            else:
+                go_right = _route_right(b, t, cm[node])
             node = node * 2 + 1 + go_right.long()
         leaf = node - (2 ** self.depth - 1)
         lv = torch.tensor(self.leaf_value, device=bins.device)
         return lv[leaf]
+
+
+def _route_right(b: torch.Tensor, t: torch.Tensor, m: torch.Tensor
+                 ) -> torch.Tensor:
+    """go-right per sample from its bin b, and its node's threshold t and
+    category mask m (int64): the three node kinds of GBTree."""
+    in_mask = ((m >> b.clamp(0, 63)) & 1).bool() & (b < 64)
+    return torch.where(t >= 0, b > t, (t == -2) & in_mask)
 
 
 def encode_trees(items, depth: int) -> torch.Tensor:
@@ -79,48 +110,129 @@ def encode_trees(items, depth: int) -> torch.Tensor:
     int32 row per tree = [key, feature[2^d-1], threshold[2^d-1],
     bitcast(leaf f32)[2^d]]. Replaces the pickled wire (GBTreeListCodec in
     the reference, mlapps/serialization/) with a flat all-gatherable
-    tensor — VERDICT r01 weak #4."""
+    tensor — VERDICT r01 weak #4.
+
+    If any tree of the batch has a cat_mask, every row is extended by
+    2 * (2^d - 1) words, the low and the high half of each node's mask as
+    bit patterns (a tree without masks sends zeros), so the rows of a batch
+    are always equally long."""
     ni = (1 << depth) - 1
+    with_masks = any(t.cat_mask is not None for _, t in items)
     rows = []
     for key, t in items:
         assert t.depth == depth
-        rows.append(torch.cat([
+        parts = [
             torch.tensor([key], dtype=torch.int32),
             torch.tensor(t.feature, dtype=torch.int32),
             torch.tensor(t.threshold, dtype=torch.int32),
             torch.tensor(t.leaf_value,
-                         dtype=torch.float32).view(torch.int32)]))
+                         dtype=torch.float32).view(torch.int32)]
+        if with_masks:
+            m = torch.tensor(t.cat_mask if t.cat_mask is not None
+                             else [0] * ni, dtype=torch.int64)
+            halves = m.view(torch.int32).view(ni, 2)    # little-endian
+            parts += [halves[:, 0].contiguous(), halves[:, 1].contiguous()]
+        rows.append(torch.cat(parts))
     return torch.stack(rows) if rows else torch.empty((0, 1 + 2 * ni +
                                                        (1 << depth)),
                                                       dtype=torch.int32)
 
 
-def decode_trees(enc: torch.Tensor, depth: int):
+def decode_trees(enc, depth: int):
+    """enc: the [n, row] tensor of encode_trees, or a sequence of 1-D rows.
+    A row of 1 + 2 ni + 2^d words is a tree without masks; 2 ni words more
+    carry the masks."""
     ni = (1 << depth) - 1
+    base = 1 + 2 * ni + (1 << depth)
     out = []
-    for row in enc.cpu():
+    rows = enc.cpu() if isinstance(enc, torch.Tensor) else enc
+    for row in rows:
+        row = row.cpu()
+        assert row.shape[0] in (base, base + 2 * ni), row.shape
         key = int(row[0])
         feat = row[1:1 + ni].tolist()
         thr = row[1 + ni:1 + 2 * ni].tolist()
-        lv = row[1 + 2 * ni:].view(torch.float32).tolist()
+        lv = row[1 + 2 * ni:base].view(torch.float32).tolist()
+        masks = None
+        if row.shape[0] > base:
+            halves = torch.stack([row[base:base + ni],
+                                  row[base + ni:base + 2 * ni]], dim=1)
+            masks = halves.contiguous().view(torch.int64).view(ni).tolist()
         out.append((key, GBTree(depth=depth, feature=feat, threshold=thr,
-                                leaf_value=lv)))
+                                leaf_value=lv, cat_mask=masks)))
     return out
 
 
-def quantize(X: torch.Tensor, num_bins: int) -> torch.Tensor:
+MAX_CATEGORIES = 64    # a node's categories are one 64-bit mask
+CAT_EFFECT = 3.0       # synthetic data: size of the category-subset term
+
+
+def feature_types(app_args: dict) -> Optional[torch.Tensor]:
+    """The job's feature types: int32 [num_features], 0 = continuous,
+    non-zero = categorical (the number of categories), or None when no
+    feature is categorical. With `input` they come from the metadata file
+    (`metadata`, default <input>.meta; reference GBTMetadataParser): entries
+    at or past num_features (the y-value entry) are ignored, a feature the
+    file does not name is continuous, a missing file means no types.
+    Synthetic data: the last num_categorical features."""
+    F = int(app_args.get("num_features", 32))
+    types = torch.zeros(F, dtype=torch.int32)
+    if app_args.get("input"):
+        from harmony_amd import dataloader as dl
+
+        meta_path = app_args.get("metadata", app_args["input"] + ".meta")
+        try:
+            meta = dl.parse_gbt_meta(dl.read_split(meta_path, (0, 1 << 50)))
+        except OSError:
+            meta = {}
+        for i, t in meta.items():
+            if 0 <= i < F:
+                types[i] = t
+    else:
+        nc = int(app_args.get("num_categorical", 0))
+        if nc > 0:
+            types[max(0, F - nc):] = int(app_args.get("num_categories", 8))
+    return types if bool((types != 0).any()) else None
+
+
+def quantize(X: torch.Tensor, num_bins: int,
+             feature_types: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-feature quantile binning (reference pre-sorts per feature for the
-    exact scan; binning is the histogram-method equivalent)."""
+    exact scan; binning is the histogram-method equivalent). A column that
+    feature_types marks categorical is not binned: bin = int(value), which
+    must be an integer in 0 .. min(num_bins, 64) - 1."""
     qs = torch.quantile(X, torch.linspace(0, 1, num_bins + 1,
                                           device=X.device)[1:-1], dim=0)
-    return torch.searchsorted(qs.t().contiguous(), X.t().contiguous()
+    bins = torch.searchsorted(qs.t().contiguous(), X.t().contiguous()
                               ).t().contiguous().clamp_(0, num_bins - 1)
+    if feature_types is None:
+        return bins
+    limit = min(num_bins, MAX_CATEGORIES)
+    for f in (feature_types != 0).nonzero().flatten().tolist():
+        col = X[:, f]
+        bad = (col < 0) | (col != col.floor()) | (col >= limit) \
+            | ~torch.isfinite(col)
+        if bool(bad.any()):
+            v = float(col[bad][0])
+            raise ValueError(
+                f"categorical feature {f}: value {v!r} is not an integer in "
+                f"0..{limit - 1} (cardinality is limited by num_bins = "
+                f"{num_bins} and {MAX_CATEGORIES})")
+        bins[:, f] = col.long()
+    return bins
 
 
 def build_tree(bins: torch.Tensor, resid: torch.Tensor, num_bins: int,
-               max_depth: int, lam: float) -> GBTree:
+               max_depth: int, lam: float,
+               feature_types: Optional[torch.Tensor] = None) -> GBTree:
     """Level-wise histogram tree build (K10): one scatter-add per level for
-    all nodes' (count, sum) histograms; split gain = variance reduction."""
+    all nodes' (count, sum) histograms; split gain = variance reduction.
+    With feature_types (even all zeros) the split search is ops.gbt_best_split
+    (K10b), which also searches category subsets; without, the tensor-op
+    threshold search below."""
+    if feature_types is not None:
+        return _build_tree_typed(bins, resid, num_bins, max_depth, lam,
+                                 feature_types)
     B, F = bins.shape
     dev = bins.device
     node = torch.zeros(B, dtype=torch.int64, device=dev)   # node per sample
@@ -171,6 +283,43 @@ def build_tree(bins: torch.Tensor, resid: torch.Tensor, num_bins: int,
     return GBTree(max_depth, feature, threshold, values)
 
 
+def _build_tree_typed(bins: torch.Tensor, resid: torch.Tensor, num_bins: int,
+                      max_depth: int, lam: float,
+                      feature_types: torch.Tensor) -> GBTree:
+    """build_tree over typed features: per level K10, K10b, ONE host copy of
+    the level's (feature, threshold, mask) rows for the tree's lists, and
+    the routing on the device from the same tensors."""
+    B, F = bins.shape
+    dev = bins.device
+    ftype = feature_types.to(device=dev, dtype=torch.int32)
+    node = torch.zeros(B, dtype=torch.int64, device=dev)
+    feature: List[int] = []
+    threshold: List[int] = []
+    cat_mask: List[int] = []
+    for level in range(max_depth):
+        first = 2 ** level - 1
+        n_nodes = 2 ** level
+        local = node - first
+        cnt, s = ops.gbt_hist(bins, resid, local, n_nodes, num_bins)
+        feat, thr, mask, _ = ops.gbt_best_split(cnt, s, ftype, lam)
+        feat, thr = feat.long(), thr.long()
+        f_l, t_l, m_l = torch.stack([feat, thr, mask]).tolist()
+        feature += f_l
+        threshold += t_l
+        cat_mask += m_l
+        b = bins.gather(1, feat[local].unsqueeze(1)).squeeze(1)
+        go_right = _route_right(b, thr[local], mask[local])
+        node = node * 2 + 1 + go_right.long()
+    first_leaf = 2 ** max_depth - 1
+    n_leaves = 2 ** max_depth
+    leaf = node - first_leaf
+    cnt = torch.zeros(n_leaves, device=dev).scatter_add_(
+        0, leaf, torch.ones_like(resid))
+    s = torch.zeros(n_leaves, device=dev).scatter_add_(0, leaf, resid)
+    values = (s / (cnt + lam)).tolist()
+    return GBTree(max_depth, feature, threshold, values, cat_mask)
+
+
 class GBTTrainer(Trainer):
     def __init__(self, ctx: TrainerContext):
         super().__init__(ctx)
@@ -186,6 +335,10 @@ class GBTTrainer(Trainer):
         # trees added since the block's last visit are applied — O(new)
         # instead of O(total) trees per batch
         self._pred_cache: dict = {}
+        # resolved once; every build_tree call gets them (None: no
+        # categorical feature, the untyped split search)
+        ft = feature_types(self.a)
+        self.feature_types = None if ft is None else ft.to(ctx.device)
 
     def pull_model(self) -> None:
         # pullAllTrees (reference :767). The forest is APPEND-ONLY, so
@@ -211,9 +364,12 @@ class GBTTrainer(Trainer):
         # a stopped worker still contributes to the equal-count tree
         # all-gather: a pass-through tree predicting 0 (harmless append)
         d = self.a["max_depth"]
+        # with typed features every rank encodes the extended tree row
+        typed = getattr(self, "feature_types", None) is not None
         return GBTree(depth=d, feature=[0] * ((1 << d) - 1),
                       threshold=[-1] * ((1 << d) - 1),
-                      leaf_value=[0.0] * (1 << d))
+                      leaf_value=[0.0] * (1 << d),
+                      cat_mask=[0] * ((1 << d) - 1) if typed else None)
 
     def local_compute(self) -> None:
         if self.batch[0].shape[0] == 0:
@@ -243,7 +399,8 @@ class GBTTrainer(Trainer):
         resid = y - pred
         self._mse = float((resid * resid).mean())
         self.new_tree = build_tree(bins, resid, a["num_bins"], a["max_depth"],
-                                   a["lam"])
+                                   a["lam"],
+                                   getattr(self, "feature_types", None))
 
     def _compute_multiclass(self) -> None:
         """One-vs-all boosting (reference GBTTrainer multi-label: one GBTree
@@ -270,7 +427,8 @@ class GBTTrainer(Trainer):
             scores.append(pred)
             self.new_trees.append(
                 (c, build_tree(bins, resid, a["num_bins"], a["max_depth"],
-                               a["lam"])))
+                               a["lam"],
+                               getattr(self, "feature_types", None))))
         pred_cls = torch.stack(scores, dim=1).argmax(dim=1)
         self._mse = float((pred_cls != y.long()).float().mean())  # error rate
 
@@ -316,25 +474,21 @@ def make_batches(job: JobConfig, rank: int, device: torch.device,
     a = defaults(job)
     F = a["num_features"]
     n_blocks = job.num_worker_blocks or job.num_mini_batches
+    ftypes = feature_types(a)
     if job.app_args.get("input"):
         # sample_gbt libsvm-style rows (+ optional .meta feature types,
-        # reference GBTMetadataParser)
+        # reference GBTMetadataParser: a categorical column stays unbinned)
         from harmony_amd import dataloader as dl
 
         X, y = dl.parse_libsvm_split(job.app_args["input"], rank,
                                      world_size, F)
-        meta_path = job.app_args.get("metadata",
-                                     job.app_args["input"] + ".meta")
-        try:
-            meta = dl.parse_gbt_meta(dl.read_split(meta_path, (0, 1 << 50)))
-        except OSError:
-            meta = {}
-        _ = meta  # feature types: categorical handling is binning-equivalent
         blocks = []
         for xb, yb in zip(torch.chunk(X, n_blocks), torch.chunk(y, n_blocks)):
-            bins = quantize(xb, a["num_bins"])
+            bins = quantize(xb, a["num_bins"], ftypes)
             blocks.append((bins.to(device), yb.to(device)))
         return blocks
+    nc = min(int(a["num_categorical"]), F)
+    ncat = int(a["num_categories"])
     g = torch.Generator().manual_seed(stable_seed(job.job_id, "data", rank))
     w = torch.randn(F, generator=g)
     mc = a["objective"] == "multiclass"
@@ -344,15 +498,32 @@ def make_batches(job: JobConfig, rank: int, device: torch.device,
     n_blocks = job.num_worker_blocks or job.num_mini_batches
     for _ in range(n_blocks):
         X = torch.randn(a["batch_size"], F, generator=g)
+        if nc > 0:
+            # the last nc features are category ids; they stay out of the
+            # linear term, and the first of them acts through a fixed
+            # non-contiguous subset of its categories (ids = 1 mod 3), which
+            # no single ordinal threshold isolates
+            cats = torch.randint(0, ncat, (a["batch_size"], nc), generator=g)
+            Xc = X.clone()
+            Xc[:, F - nc:] = cats.float()
+            X[:, F - nc:] = 0.0
+            effect = CAT_EFFECT * ((cats[:, 0] % 3 == 1).float() * 2 - 1)
         if mc:
             # separable class labels: argmax of per-class linear scores
-            y = (X @ W.t() + a["noise"]
+            score = X @ W.t()
+            if nc > 0:
+                score[:, 0] += effect
+            y = (score + a["noise"]
                  * torch.randn(a["batch_size"], a["num_classes"],
                                generator=g)).argmax(dim=1).float()
         else:
-            y = (X @ w + torch.sin(3 * X[:, 0]) * 2
-                 + a["noise"] * torch.randn(a["batch_size"], generator=g))
-        bins = quantize(X, a["num_bins"])
+            y = X @ w + torch.sin(3 * X[:, 0]) * 2
+            if nc > 0:
+                y = y + effect
+            y = y + a["noise"] * torch.randn(a["batch_size"], generator=g)
+        if nc > 0:
+            X = Xc
+        bins = quantize(X, a["num_bins"], ftypes)
         blocks.append((bins.to(device), y.to(device)))
     return blocks
 

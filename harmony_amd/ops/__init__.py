@@ -15,6 +15,8 @@ Kernel inventory (reference hot loops):
   K4s mlr_sparse_fwd/grad MLRTrainer.java:374-398 over SparseVector rows
   K7  lda_gibbs           SparseLDASampler.java:141-274
   K9  scatter-apply       LDAETModelUpdateFunction.java:43-64
+  K10 gbt_hist            GBTTrainer.java:244+ (histogram method)
+  K10b gbt_best_split     GBTTrainer.java bestSplitRealFeature/LabelFeature
   K11 lasso_cd            LassoTrainer.java:164-190
   K11s lasso_cd_sparse    LassoTrainer.java:164-208 over SparseVector columns
   K12 loss reductions     NMFTrainer.java:414-456 etc.
@@ -871,6 +873,87 @@ def gbt_hist(bins: torch.Tensor, resid: torch.Tensor, node: torch.Tensor,
     s.scatter_add_(0, idx.reshape(-1),
                    resid.float().unsqueeze(1).expand(B, F).reshape(-1))
     return (cnt.view(n_nodes, F, num_bins), s.view(n_nodes, F, num_bins))
+
+
+GBT_NO_CANDIDATE = -1e30     # gain of an invalid split candidate
+GBT_MIN_GAIN = 1e-12         # a split must gain more than this
+GBT_SPLIT_MAX_BINS = 64      # K10b: one lane per bin or category
+
+
+def gbt_best_split(cnt: torch.Tensor, s: torch.Tensor, ftype: torch.Tensor,
+                   lam: float) -> Tuple[torch.Tensor, torch.Tensor,
+                                        torch.Tensor, torch.Tensor]:
+    """Best split per node of one tree level from its K10 histograms (K10b,
+    ops/csrc/gbt_split.hip; reference GBTTrainer.java bestSplitRealFeature /
+    bestSplitLabelFeature). cnt, s: float32 [n_nodes, F, nb]; ftype: int32
+    [F], 0 = continuous, non-zero = categorical.
+    Returns (feature int32, threshold int32, mask int64, gain float32), each
+    [n_nodes].
+
+    Continuous feature: candidates b = 0..nb-2, left = bins <= b. Categorical
+    feature: the live categories (cnt > 0) ordered by mean s / cnt ascending,
+    ties by category id; candidates p = 1..L-1, left = the first p of that
+    order, and the mask holds exactly the bits of the others. A candidate is
+    valid iff both sides have cnt > 0. gain = sl^2/(cl+lam) + sr^2/(cr+lam)
+    - stot^2/(ctot+lam); the best is the largest over all features and
+    candidates, ties to the lowest feature, then the lowest candidate. A
+    continuous winner gives threshold = b, mask = 0; a categorical one
+    threshold = -2. No valid candidate, or a best gain <= 1e-12, gives
+    feature 0, threshold -1, mask 0, gain 0.
+
+    CPU tensors, HARMONY_FORCE_TORCH_OPS=1 and nb > 64 take the tensor ops
+    below, which are the kernel's test oracle."""
+    n_nodes, F, nb = cnt.shape
+    if _use_hip(cnt) and nb <= GBT_SPLIT_MAX_BINS:
+        return tuple(_hip.gbt_best_split(
+            cnt.contiguous(), s.contiguous(),
+            ftype.to(device=cnt.device, dtype=torch.int32).contiguous(),
+            float(lam)))
+    dev = cnt.device
+    if nb < 2:
+        no = torch.zeros(n_nodes, dtype=torch.int32, device=dev)
+        return (no, no - 1, no.long(), no.float())
+    cat = (ftype.to(dev) != 0).view(1, F, 1)
+    live = cnt > 0
+    ident = torch.arange(nb, device=dev).expand(n_nodes, F, nb)
+    # (mean, id) order of the live categories, dead ones behind them
+    mean = torch.where(live, s / cnt, torch.full_like(s, float("inf")))
+    order = torch.where(cat, mean.sort(dim=2, stable=True).indices, ident)
+    ccum = cnt.gather(2, order).cumsum(dim=2)
+    scum = s.gather(2, order).cumsum(dim=2)
+    ctot, stot = ccum[:, :, -1:], scum[:, :, -1:]
+    cl, sl = ccum[:, :, :-1], scum[:, :, :-1]
+    cr, sr = ctot - cl, stot - sl
+    gain = (sl * sl / (cl + lam) + sr * sr / (cr + lam)
+            - stot * stot / (ctot + lam))
+    gain = torch.where((cl > 0) & (cr > 0), gain,
+                       torch.full_like(gain, GBT_NO_CANDIDATE))
+    flat = gain.reshape(n_nodes, -1)
+    best_gain = flat.max(dim=1).values
+    pos = torch.arange(flat.shape[1], device=dev).expand_as(flat)
+    best = torch.where(flat == best_gain.unsqueeze(1), pos,
+                       torch.full_like(pos, flat.shape[1])).min(dim=1).values
+    bf = best // (nb - 1)
+    bp = best % (nb - 1)
+    split = best_gain > GBT_MIN_GAIN
+    wcat = split & cat.view(F)[bf]
+    # right side of the winner: live categories ranked behind candidate bp
+    sel = bf.view(n_nodes, 1, 1).expand(n_nodes, 1, nb)
+    rank = torch.empty_like(order).scatter_(2, order, ident)
+    right = (live.gather(1, sel).squeeze(1)
+             & (rank.gather(1, sel).squeeze(1) > bp.unsqueeze(1)))
+    # distinct bits, so the sum is their union (bit 63 is the sign bit); a
+    # category id above 63 has no bit and always goes left
+    ids = torch.arange(nb, device=dev)
+    bit = (torch.ones(nb, dtype=torch.int64, device=dev)
+           << ids.clamp(max=63)) * (ids < 64)
+    mask = (right.long() * bit).sum(dim=1)
+    zero = torch.zeros_like(best)
+    return (torch.where(split, bf, zero).to(torch.int32),
+            torch.where(wcat, zero - 2,
+                        torch.where(split, bp, zero - 1)).to(torch.int32),
+            torch.where(wcat, mask, zero),
+            torch.where(split, best_gain, torch.zeros_like(best_gain)))
 
 
 def lasso_cd(X: torch.Tensor, r: torch.Tensor, w: torch.Tensor,

@@ -104,6 +104,8 @@ std::vector<torch::Tensor> os_ring_drain(int64_t base, int64_t W,
                                          int64_t max_per);
 void gbt_hist(torch::Tensor bins, torch::Tensor resid, torch::Tensor node,
               torch::Tensor cnt, torch::Tensor sum);
+std::vector<torch::Tensor> gbt_best_split(torch::Tensor cnt, torch::Tensor s,
+                                          torch::Tensor ftype, double lam);
 void scatter_apply(torch::Tensor shard, torch::Tensor rows,
                    torch::Tensor deltas, int64_t mode, double step,
                    double maxval);
@@ -162,6 +164,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lda_mh_wave_packed", &lda_mh_wave_packed,
         "wave-per-doc MH sweep over packed tables, optional fused apply (K7d)");
   m.def("gbt_hist", &gbt_hist, "GBT level histogram build (K10)");
+  m.def("gbt_best_split", &gbt_best_split,
+        "GBT per-node best split, continuous and categorical (K10b)");
   m.def("lasso_cd", &lasso_cd, "Lasso persistent CD sweep (K11)");
   m.def("lasso_cd_sparse", &lasso_cd_sparse,
         "Lasso CD sweep over a batch's column index (K11s)");
