@@ -258,14 +258,13 @@ class LDATrainer(Trainer):
     def _is_alias(self) -> bool:
         return self.a["sampler"] in ("alias", "alias_wave")
 
-    def _ensure_alias(self) -> None:
-        # two-level alias tables over the word factor (K7b), rebuilt every
-        # alias_refresh uses OF THIS BLOCK (tables index the block's local
-        # word ids) — the MH acceptance corrects for table staleness with
-        # the stored proposal density qv. Built in the COMP phase: the
-        # build is pure local compute, and keeping it inside the NET
-        # ticket (round 1) serialized co-located jobs behind ~300 us of
-        # kernel per refresh.
+    def _alias_tables(self, build):
+        """What `build()` returned for this block, rebuilt every
+        alias_refresh uses OF THIS BLOCK (tables index the block's local
+        word ids) — the MH acceptance corrects for table staleness with the
+        stored proposal density qv. Built in the COMP phase: the build is
+        pure local compute, and keeping it inside the NET ticket (round 1)
+        serialized co-located jobs behind ~300 us of kernel per refresh."""
         if not hasattr(self, "_alias_cache"):
             self._alias_cache = {}
             self._alias_age = {}
@@ -273,100 +272,72 @@ class LDATrainer(Trainer):
         refresh = max(1, int(self.a["alias_refresh"]))
         age = self._alias_age.get(bid, refresh)
         if age >= refresh:
-            self._alias_cache[bid] = ops.lda_alias_build(
-                self.word_topic, self.topic_sum, self.a["beta"],
-                self.a["num_vocabs"])
+            self._alias_cache[bid] = build()
             age = 0
         self._alias_age[bid] = age + 1
-        self._alias = self._alias_cache[bid]
+        return self._alias_cache[bid]
 
-    def _ensure_alias_packed(self, rec, top, fused: bool) -> None:
-        # same refresh schedule as _ensure_alias; only invden is kept
-        # beside the packed tables
-        if not hasattr(self, "_invden_cache"):
-            self._invden_cache = {}
-            self._alias_age = {}
-        bid = self._block_idx
-        refresh = max(1, int(self.a["alias_refresh"]))
-        age = self._alias_age.get(bid, refresh)
-        if age >= refresh:
-            if fused:
-                b = self.batch
-                shard = self.accessor.table.shard
+    def _sweep_alias(self, dt, z, seed) -> None:
+        # two-level alias tables over the word factor (K7b), legacy arrays
+        b, a = self.batch, self.a
+        prob, alias, tprob, talias, qv, _, invden = self._alias_tables(
+            lambda: ops.lda_alias_build(self.word_topic, self.topic_sum,
+                                        a["beta"], a["num_vocabs"]))
+        fn = ops.lda_mh_wave if a["sampler"] == "alias_wave" else ops.lda_mh
+        # NOTE: invden/qv index LOCAL word ids of the batch on which the
+        # tables were built; with one static key set per block this is
+        # consistent across refreshes of the same block
+        fn(dt, self.word_topic, invden, prob, alias, tprob, talias, qv,
+           b.doc_offsets, b.word_local, z, a["alpha"], a["beta"], seed)
+
+    def _sweep_packed(self, dt, z, seed, fused: bool) -> None:
+        # packed tables (K7d) are written in place; only invden is cached
+        b, a = self.batch, self.a
+        rec, top = self._packed_tables(b)
+        shard = self.accessor.table.shard if fused else None
+
+        def build():
+            if fused:       # word rows and summary row from the shard in place
                 src, rows, nk = shard, b.row_of_local, shard[b.summary_row]
             else:
                 src, rows, nk = self.word_topic, None, self.topic_sum
-            self._invden_cache[bid], _ = ops.lda_alias_build_packed(
-                src, rows, nk, self.a["beta"], self.a["num_vocabs"], rec, top)
-            age = 0
-        self._alias_age[bid] = age + 1
+            return ops.lda_alias_build_packed(
+                src, rows, nk, a["beta"], a["num_vocabs"], rec, top)[0]
 
-    def _local_compute_packed(self) -> None:
-        b = self.batch
-        z = self._assignments[self._block_idx]
-        fused = self._single_owner()
-        self._step += 1
-        if b.docs_contiguous:
-            dt = self.doc_topic[b.doc_lo:b.doc_lo + b.num_examples]
-        else:
-            dt = self.doc_topic[b.doc_ids]      # gather copy
-        rec, top = self._packed_tables(b)
-        self._ensure_alias_packed(rec, top, fused)
-        invden = self._invden_cache[self._block_idx]
-        seed = self._epoch_seed + self._step
-        if fused:
-            # the sweep applies its own +/-1 to the shard: no copy of the
-            # old assignments, nothing left for push_update
-            ops.lda_mh_wave_packed(
-                dt, self.word_topic, rec, top, invden, b.doc_offsets,
-                b.word_local32, z, self.a["alpha"], self.a["beta"], seed,
-                shard=self.accessor.table.shard,
-                row_of_local=b.row_of_local, summary_row=b.summary_row)
-            self._old_z = None
-        else:
-            self._old_z = z.clone()
-            ops.lda_mh_wave_packed(
-                dt, self.word_topic, rec, top, invden, b.doc_offsets,
-                b.word_local32, z, self.a["alpha"], self.a["beta"], seed)
-        if not b.docs_contiguous:
-            self.doc_topic[b.doc_ids] = dt      # write back
-        self._new_z = z
+        invden = self._alias_tables(build)
+        kw = (dict(shard=shard, row_of_local=b.row_of_local,
+                   summary_row=b.summary_row) if fused else {})
+        ops.lda_mh_wave_packed(dt, self.word_topic, rec, top, invden,
+                               b.doc_offsets, b.word_local32, z, a["alpha"],
+                               a["beta"], seed, **kw)
 
     def local_compute(self) -> None:
-        if self._use_packed():
-            self._local_compute_packed()
-            return
         b = self.batch
         z = self._assignments[self._block_idx]
-        old = z.clone()
+        packed = self._use_packed()
+        # the fused sweep (single-owner packed path) applies its own +/-1 to
+        # the shard: no copy of the old assignments, nothing left for
+        # push_update
+        fused = packed and self._single_owner()
+        self._old_z = None if fused else z.clone()
         self._step += 1
+        seed = self._epoch_seed + self._step
         if b.docs_contiguous:
             # in-place slice view: the sampler kernels mutate doc_topic
             # directly (no gather/scatter round trip)
             dt = self.doc_topic[b.doc_lo:b.doc_lo + b.num_examples]
         else:
             dt = self.doc_topic[b.doc_ids]      # gather copy
-        if self._is_alias():
-            self._ensure_alias()
-            prob, alias, tprob, talias, qv, _, invden = self._alias
-            fn = (ops.lda_mh_wave if self.a["sampler"] == "alias_wave"
-                  else ops.lda_mh)
-            # NOTE: invden/qv index LOCAL word ids of the batch on which the
-            # tables were built; with one static key set per block this is
-            # consistent across refreshes of the same block
-            fn(dt, self.word_topic, invden, prob, alias, tprob,
-               talias, qv, b.doc_offsets, b.word_local, z,
-               self.a["alpha"], self.a["beta"],
-               self._epoch_seed + self._step)
+        if packed:
+            self._sweep_packed(dt, z, seed, fused)
+        elif self._is_alias():
+            self._sweep_alias(dt, z, seed)
         else:
-            ops.lda_gibbs(dt, self.word_topic,
-                          self.topic_sum, b.doc_offsets, b.word_local, z,
-                          self.a["alpha"], self.a["beta"],
-                          self.a["num_vocabs"],
-                          self._epoch_seed + self._step)
+            ops.lda_gibbs(dt, self.word_topic, self.topic_sum, b.doc_offsets,
+                          b.word_local, z, self.a["alpha"], self.a["beta"],
+                          self.a["num_vocabs"], seed)
         if not b.docs_contiguous:
             self.doc_topic[b.doc_ids] = dt      # write back
-        self._old_z = old
         self._new_z = z
 
     def push_update(self) -> None:

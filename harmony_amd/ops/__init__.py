@@ -608,7 +608,11 @@ def lda_alias_build(word_topic: torch.Tensor, topic_sum: torch.Tensor,
         seg_mass = (cseg[:, :, i] * iseg[:, i] + seg_mass.double()).float()
     total = _butterfly_sum64(seg_mass)
     qv = (p * (1.0 / total).unsqueeze(1)).contiguous()   # encoded density
-    sscale = torch.where(seg_mass > 0, S / seg_mass,
+    # tensor / tensor: torch evaluates `S / seg_mass` as reciprocal * S,
+    # which rounds twice and differs from the kernel's one division unless
+    # S is a power of two
+    sscale = torch.where(seg_mass > 0,
+                         torch.full_like(seg_mass, float(S)) / seg_mass,
                          torch.zeros_like(seg_mass))
     prob = (pseg * sscale.unsqueeze(2)).reshape(rows, K).contiguous()
     alias = torch.empty((rows, K), dtype=torch.int32)
