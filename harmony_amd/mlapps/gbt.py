@@ -30,6 +30,15 @@ column is not binned (bin = category id, so at most min(num_bins, 64)
 categories) and is split by a SUBSET of its categories (K10b, reference
 bestSplitLabelFeature), stored per node as a 64-bit mask. Without a
 categorical feature nothing changes.
+
+sparse=true (default false; nnz_per_row for synthetic data) keeps every
+block as a SparseBins (mlapps/sparse_bins.py; reference GBTETDataParser
+createSparse): CSR input is binned without densifying, with the edges
+quantize gives the densified block, the level histograms come from K10s
+(ops.gbt_hist_sparse) over the features present in the block, and routing
+and prediction look a bin up instead of gathering it from a dense row. On
+the same data the trees equal the dense path's; memory and time follow nnz
+and the number of present features, never B * F.
 """
 
 from __future__ import annotations
@@ -43,6 +52,7 @@ from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
 from harmony_amd.et.table import ObjectTable
+from harmony_amd.mlapps.sparse_bins import SparseBins
 from harmony_amd.utils import stable_seed
 from harmony_amd import ops
 
@@ -52,7 +62,8 @@ MODEL_TABLE = "gbt_model"
 def defaults(job: JobConfig) -> dict:
     a = dict(num_features=32, batch_size=4096, num_bins=64, max_depth=4,
              step_size=0.1, lam=1.0, noise=0.1, objective="regression",
-             num_classes=3, num_categorical=0, num_categories=8)
+             num_classes=3, num_categorical=0, num_categories=8,
+             sparse="false", nnz_per_row=32)
     a.update(job.app_args)
     return a
 
@@ -73,8 +84,10 @@ class GBTree:
     leaf_value: List[float]     # [2^d]
     cat_mask: Optional[List[int]] = None   # [2^d - 1] signed 64-bit masks
 
-    def predict_bins(self, bins: torch.Tensor) -> torch.Tensor:
-        """bins: [B, F] int64 quantized features -> [B] predictions."""
+    def predict_bins(self, bins) -> torch.Tensor:
+        """bins: [B, F] int64 quantized features, or a SparseBins of that
+        shape (a bin is then looked up, not gathered) -> [B] predictions."""
+        sparse = isinstance(bins, SparseBins)
         B = bins.shape[0]
         node = torch.zeros(B, dtype=torch.int64, device=bins.device)
         feat = torch.tensor(self.feature, device=bins.device)
@@ -86,7 +99,8 @@ class GBTree:
         for _ in range(self.depth):
             f = feat[node]
             t = thr[node]
-            b = bins.gather(1, f.unsqueeze(1)).squeeze(1)
+            b = bins.bin_of(f) if sparse else \
+                bins.gather(1, f.unsqueeze(1)).squeeze(1)
             if cm is None:
                 go_right = (b > t) & (t >= 0)
             else:
@@ -229,7 +243,12 @@ def build_tree(bins: torch.Tensor, resid: torch.Tensor, num_bins: int,
     all nodes' (count, sum) histograms; split gain = variance reduction.
     With feature_types (even all zeros) the split search is ops.gbt_best_split
     (K10b), which also searches category subsets; without, the tensor-op
-    threshold search below."""
+    threshold search below. A SparseBins batch is built by K10s and K10b
+    over its present features (_build_tree_sparse) and gives the trees the
+    dense bins of the same data give."""
+    if isinstance(bins, SparseBins):
+        return _build_tree_sparse(bins, resid, num_bins, max_depth, lam,
+                                  feature_types)
     if feature_types is not None:
         return _build_tree_typed(bins, resid, num_bins, max_depth, lam,
                                  feature_types)
@@ -318,6 +337,62 @@ def _build_tree_typed(bins: torch.Tensor, resid: torch.Tensor, num_bins: int,
     s = torch.zeros(n_leaves, device=dev).scatter_add_(0, leaf, resid)
     values = (s / (cnt + lam)).tolist()
     return GBTree(max_depth, feature, threshold, values, cat_mask)
+
+
+def _build_tree_sparse(sb: SparseBins, resid: torch.Tensor, num_bins: int,
+                       max_depth: int, lam: float,
+                       feature_types: Optional[torch.Tensor]) -> GBTree:
+    """build_tree over a SparseBins: per level K10s over the batch's present
+    features, K10b on that [n_nodes, nf, nb] histogram, the winner mapped
+    back through feat_ids, and routing by bin lookup. A feature absent from
+    the batch has one populated bin and so no valid candidate: leaving it
+    out changes no winner, and feat_ids ascending keeps the lowest-feature
+    tie rule. Without feature types the types are zeros and the tree has
+    cat_mask = None, as the dense builder's."""
+    B = sb.shape[0]
+    dev = sb.device
+    ids = sb.feat_ids.long()
+    nf = ids.shape[0]
+    if feature_types is None:
+        ftype = torch.zeros(nf, dtype=torch.int32, device=dev)
+    else:
+        ftype = feature_types.to(device=dev, dtype=torch.int32)[ids]
+    node = torch.zeros(B, dtype=torch.int64, device=dev)
+    feature: List[int] = []
+    threshold: List[int] = []
+    cat_mask: List[int] = []
+    for level in range(max_depth):
+        first = 2 ** level - 1
+        n_nodes = 2 ** level
+        local = node - first
+        if nf == 0:
+            feat = torch.zeros(n_nodes, dtype=torch.int64, device=dev)
+            thr, mask = feat - 1, feat.clone()
+        else:
+            cnt, s = ops.gbt_hist_sparse(
+                sb.feat_ptr, sb.feat_row, sb.feat_bin, sb.feat_idx,
+                sb.zero_bin, resid, local, n_nodes, num_bins)
+            feat, thr, mask, _ = ops.gbt_best_split(cnt, s, ftype, lam)
+            thr = thr.long()
+            # a no-split node reports feature 0, as the dense builder does
+            feat = torch.where(thr == -1, torch.zeros_like(thr),
+                               ids[feat.long()])
+        f_l, t_l, m_l = torch.stack([feat, thr, mask]).tolist()
+        feature += f_l
+        threshold += t_l
+        cat_mask += m_l
+        go_right = _route_right(sb.bin_of(feat[local]), thr[local],
+                                mask[local])
+        node = node * 2 + 1 + go_right.long()
+    first_leaf = 2 ** max_depth - 1
+    n_leaves = 2 ** max_depth
+    leaf = node - first_leaf
+    cnt = torch.zeros(n_leaves, device=dev).scatter_add_(
+        0, leaf, torch.ones_like(resid))
+    s = torch.zeros(n_leaves, device=dev).scatter_add_(0, leaf, resid)
+    values = (s / (cnt + lam)).tolist()
+    return GBTree(max_depth, feature, threshold, values,
+                  cat_mask if feature_types is not None else None)
 
 
 class GBTTrainer(Trainer):
@@ -469,12 +544,100 @@ class GBTTrainer(Trainer):
         return self.batch[0].shape[0]
 
 
+def _is_sparse(a: dict) -> bool:
+    return str(a.get("sparse", "")).lower() in ("true", "1")
+
+
+SPARSE_SIGNAL_COLS = 4   # synthetic sparse data: columns y depends on
+
+
+def _make_sparse_batches(job: JobConfig, a: dict, rank: int,
+                         device: torch.device, world_size: int, ftypes):
+    """make_batches for sparse=true: the same block structure as the dense
+    branch, every block a (SparseBins, y) pair, binned on the CPU from its
+    CSR rows. No tensor with B*F elements is built."""
+    F = int(a["num_features"])
+    nb = int(a["num_bins"])
+    n_blocks = max(1, job.num_worker_blocks or job.num_mini_batches)
+    blocks = []
+    if a.get("input"):
+        from harmony_amd import dataloader as dl
+
+        row_ptr, col, val, y = dl.parse_libsvm_csr_split(
+            a["input"], rank, world_size, F)
+        n = y.shape[0]
+        # torch.chunk's row ranges, so block i holds the rows the dense
+        # branch would give it
+        size = -(-n // n_blocks) if n else 0
+        for lo in range(0, max(1, n), max(1, size)):
+            hi = min(n, lo + size)
+            e0, e1 = int(row_ptr[lo]), int(row_ptr[hi])
+            x = SparseBins((row_ptr[lo:hi + 1] - e0, col[e0:e1], val[e0:e1],
+                            F), nb, ftypes)
+            blocks.append((x.to(device), y[lo:hi].float().to(device)))
+        return blocks
+    B = int(a["batch_size"])
+    nc = min(int(a["num_categorical"]), F)
+    ncat = int(a["num_categories"])
+    k = max(1, min(int(a["nnz_per_row"]), F))
+    # y depends on the first ns columns, each present in about half of the
+    # rows (an absent one counts as 0.0), so trees find something; with
+    # categorical columns the first of them is present in every row
+    ns = max(0, min(SPARSE_SIGNAL_COLS, k, F - nc))
+    cat_slot = nc > 0 and k > ns
+    mc = a["objective"] == "multiclass"
+    g = torch.Generator().manual_seed(stable_seed(job.job_id, "data", rank))
+    w = torch.randn(max(ns, 1), generator=g) * 2
+    if mc:
+        W = torch.randn(a["num_classes"], max(ns, 1), generator=g) * 2
+    for _ in range(n_blocks):
+        # per-row random feature subset: k draws, sorted, repeats dropped
+        cols = torch.randint(0, F, (B, k), generator=g)
+        if ns > 0:
+            sig = torch.rand(B, ns, generator=g) < 0.5
+            cols[:, :ns] = torch.where(sig, torch.arange(ns).expand(B, ns),
+                                       cols[:, :ns])
+        if cat_slot:
+            cols[:, ns] = F - nc
+        cols = cols.sort(dim=1).values
+        keep = torch.ones((B, k), dtype=torch.bool)
+        keep[:, 1:] = cols[:, 1:] != cols[:, :-1]
+        vals = torch.randn(B, k, generator=g)
+        if nc > 0:
+            cats = torch.randint(0, ncat, (B, k), generator=g)
+            vals = torch.where(cols >= F - nc, cats.float(), vals)
+        # the signal columns' values per row, 0.0 where absent
+        xs = torch.stack([(vals * ((cols == j) & keep)).sum(dim=1)
+                          for j in range(ns)], dim=1) if ns > 0 \
+            else torch.zeros(B, 1)
+        effect = torch.zeros(B)
+        if cat_slot:
+            c0 = (vals * ((cols == F - nc) & keep)).sum(dim=1).long()
+            effect = CAT_EFFECT * ((c0 % 3 == 1).float() * 2 - 1)
+        if mc:
+            score = xs @ W.t()
+            score[:, 0] += effect
+            y = (score + a["noise"]
+                 * torch.randn(B, a["num_classes"], generator=g)
+                 ).argmax(dim=1).float()
+        else:
+            y = xs @ w + torch.sin(3 * xs[:, 0]) * 2 + effect \
+                + a["noise"] * torch.randn(B, generator=g)
+        row_ptr = torch.zeros(B + 1, dtype=torch.int64)
+        row_ptr[1:] = torch.cumsum(keep.sum(dim=1), 0)
+        x = SparseBins((row_ptr, cols[keep], vals[keep], F), nb, ftypes)
+        blocks.append((x.to(device), y.to(device)))
+    return blocks
+
+
 def make_batches(job: JobConfig, rank: int, device: torch.device,
                  world_size: int = 1):
     a = defaults(job)
     F = a["num_features"]
     n_blocks = job.num_worker_blocks or job.num_mini_batches
     ftypes = feature_types(a)
+    if _is_sparse(a):
+        return _make_sparse_batches(job, a, rank, device, world_size, ftypes)
     if job.app_args.get("input"):
         # sample_gbt libsvm-style rows (+ optional .meta feature types,
         # reference GBTMetadataParser: a categorical column stays unbinned)
@@ -543,7 +706,8 @@ def build(job: JobConfig, ctx, cp):
         # frac<=0 -> EMPTY batch: a stopped worker (StopWorkerOp) does
         # zero work and its sparse pulls/pushes carry zero keys
         n = 0 if frac <= 0 else max(1, int(b[0].shape[0] * frac))
-        return (b[0][:n], b[1][:n])
+        x = b[0].prefix(n) if isinstance(b[0], SparseBins) else b[0][:n]
+        return (x, b[1][:n])
 
     provider = TrainingDataProvider(reslice=_reslice, local_blocks=
         make_batches(job, ctx.rank, ctx.device, ctx.world_size))

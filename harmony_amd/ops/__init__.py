@@ -17,6 +17,7 @@ Kernel inventory (reference hot loops):
   K9  scatter-apply       LDAETModelUpdateFunction.java:43-64
   K10 gbt_hist            GBTTrainer.java:244+ (histogram method)
   K10b gbt_best_split     GBTTrainer.java bestSplitRealFeature/LabelFeature
+  K10s gbt_hist_sparse    K10 over SparseVector samples (GBTETDataParser)
   K11 lasso_cd            LassoTrainer.java:164-190
   K11s lasso_cd_sparse    LassoTrainer.java:164-208 over SparseVector columns
   K12 loss reductions     NMFTrainer.java:414-456 etc.
@@ -877,6 +878,65 @@ def gbt_hist(bins: torch.Tensor, resid: torch.Tensor, node: torch.Tensor,
     s.scatter_add_(0, idx.reshape(-1),
                    resid.float().unsqueeze(1).expand(B, F).reshape(-1))
     return (cnt.view(n_nodes, F, num_bins), s.view(n_nodes, F, num_bins))
+
+
+GBT_HIST_MAX_CELLS = 8192    # K10 / K10s: n_nodes * nb cells per feature in LDS
+
+
+def gbt_hist_sparse(feat_ptr: torch.Tensor, feat_row: torch.Tensor,
+                    feat_bin: torch.Tensor, feat_idx: torch.Tensor,
+                    zero_bin: torch.Tensor, resid: torch.Tensor,
+                    node: torch.Tensor, n_nodes: int, num_bins: int
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """GBT level histogram over a binned sparse batch (K10s,
+    ops/csrc/gbt_hist_sparse.hip). The first five arguments are the column
+    side of a mlapps.sparse_bins.SparseBins: feat_ptr int64 [nf+1],
+    feat_row / feat_bin / feat_idx int32 [nnz] (row, bin and compact feature
+    index of every entry, grouped by feature), zero_bin int32 [nf] (the bin
+    of an absent entry). resid [B]; node [B] level-local node per sample.
+    Returns (cnt, sum), each float32 [n_nodes, nf, num_bins], over the
+    PRESENT features in feat_ids order.
+
+    Formula: the entries are scatter-added into their (node, feature, bin)
+    cells; then every (node, feature) adds node_cnt - sum_b cnt and
+    node_sum - sum_b sum into the feature's zero bin, where node_cnt and
+    node_sum are the per-node sample count and residual sum (one scatter
+    here). That is the share of the samples with no entry in the column.
+
+    CPU tensors, HARMONY_FORCE_TORCH_OPS=1 and levels wider than
+    n_nodes * num_bins = 8192 take the tensor ops below, which compute the
+    same formula and are the kernel's test oracle. nf == 0 launches nothing.
+    """
+    dev = resid.device
+    nf = feat_ptr.shape[0] - 1
+    resid = resid.float().contiguous()
+    node_l = node.long()
+    node_cnt = torch.zeros(n_nodes, device=dev).scatter_add_(
+        0, node_l, torch.ones_like(resid))
+    node_sum = torch.zeros(n_nodes, device=dev).scatter_add_(
+        0, node_l, resid)
+    if _use_hip(resid) and n_nodes * num_bins <= GBT_HIST_MAX_CELLS:
+        cnt, s = _hip.gbt_hist_sparse(
+            feat_ptr.contiguous(), feat_row.contiguous(),
+            feat_bin.contiguous(), feat_idx.contiguous(),
+            zero_bin.contiguous(), resid, node.int().contiguous(),
+            node_cnt, node_sum, int(num_bins))
+        return cnt, s
+    rows = feat_row.long()
+    cell = ((node_l[rows] * nf + feat_idx.long()) * num_bins
+            + feat_bin.long())
+    cnt = torch.zeros(n_nodes * nf * num_bins, device=dev)
+    s = torch.zeros_like(cnt)
+    cnt.scatter_add_(0, cell, torch.ones(cell.shape[0], device=dev))
+    s.scatter_add_(0, cell, resid[rows])
+    cnt = cnt.view(n_nodes, nf, num_bins)
+    s = s.view(n_nodes, nf, num_bins)
+    zb = zero_bin.long().view(1, nf, 1).expand(n_nodes, nf, 1)
+    cnt.scatter_add_(2, zb, node_cnt.view(-1, 1, 1)
+                     - cnt.sum(dim=2, keepdim=True))
+    s.scatter_add_(2, zb, node_sum.view(-1, 1, 1)
+                   - s.sum(dim=2, keepdim=True))
+    return cnt, s
 
 
 GBT_NO_CANDIDATE = -1e30     # gain of an invalid split candidate

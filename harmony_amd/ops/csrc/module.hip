@@ -106,6 +106,12 @@ void gbt_hist(torch::Tensor bins, torch::Tensor resid, torch::Tensor node,
               torch::Tensor cnt, torch::Tensor sum);
 std::vector<torch::Tensor> gbt_best_split(torch::Tensor cnt, torch::Tensor s,
                                           torch::Tensor ftype, double lam);
+std::vector<torch::Tensor> gbt_hist_sparse(
+    torch::Tensor feat_ptr, torch::Tensor feat_row, torch::Tensor feat_bin,
+    torch::Tensor feat_idx, torch::Tensor zero_bin, torch::Tensor resid,
+    torch::Tensor node, torch::Tensor node_cnt, torch::Tensor node_sum,
+    int64_t nb);
+int64_t gbt_hist_sparse_max_cells();
 void scatter_apply(torch::Tensor shard, torch::Tensor rows,
                    torch::Tensor deltas, int64_t mode, double step,
                    double maxval);
@@ -166,6 +172,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gbt_hist", &gbt_hist, "GBT level histogram build (K10)");
   m.def("gbt_best_split", &gbt_best_split,
         "GBT per-node best split, continuous and categorical (K10b)");
+  m.def("gbt_hist_sparse", &gbt_hist_sparse,
+        "GBT level histogram over a SparseBins column index (K10s)");
+  m.def("gbt_hist_sparse_max_cells", &gbt_hist_sparse_max_cells,
+        "widest level (n_nodes * nb) K10s keeps in LDS");
   m.def("lasso_cd", &lasso_cd, "Lasso persistent CD sweep (K11)");
   m.def("lasso_cd_sparse", &lasso_cd_sparse,
         "Lasso CD sweep over a batch's column index (K11s)");
