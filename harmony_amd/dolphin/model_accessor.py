@@ -187,3 +187,32 @@ class OneSidedAccessor:
 
     def push(self, keys, deltas, assume_unique=False):
         self.table.push(keys, deltas)
+
+
+def build_ps_table(job, cfg, ctx, cp):
+    """The PS model table of a job: with the app argument one_sided=true the
+    async PS mode's hipIpc/xGMI one-sided table (no collectives in the
+    training loop, SSP slack is the only cross-worker coupling), else a
+    collective Table on a data plane of its own."""
+    if str(job.app_args.get("one_sided", "")).lower() in ("true", "1"):
+        from harmony_amd.et.onesided import OneSidedTable
+
+        table = OneSidedTable(cfg, ctx.rank, ctx.world_size, ctx.device,
+                              store=ctx.store)
+        cp.barrier(f"{job.job_id}/os_alloc", ctx.world_size)
+        table.connect()
+        cp.barrier(f"{job.job_id}/os_conn", ctx.world_size)
+        return table
+    from harmony_amd.et.table import Table
+
+    comm = ctx.new_data_plane()
+    return Table(cfg, ctx.rank, ctx.world_size, ctx.device, comm=comm)
+
+
+def accessor_for(table):
+    """The accessor a trainer uses for its model table."""
+    from harmony_amd.et.onesided import OneSidedTable
+
+    if isinstance(table, OneSidedTable):
+        return OneSidedAccessor(table)
+    return ETModelAccessor(table)

@@ -37,10 +37,11 @@ import torch
 
 from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
-from harmony_amd.dolphin.model_accessor import ETModelAccessor
+from harmony_amd.dolphin.model_accessor import accessor_for, build_ps_table
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
-from harmony_amd.et.table import Table
-from harmony_amd.mlapps.sparse_batch import SparseBatch
+from harmony_amd.mlapps.sparse_batch import (SparseBatch, csr_row_blocks,
+                                             drop_repeats, is_sparse,
+                                             reslice)
 from harmony_amd.utils import stable_seed
 from harmony_amd import ops
 
@@ -55,8 +56,7 @@ def defaults(job: JobConfig) -> dict:
     return a
 
 
-def _is_sparse(a: dict) -> bool:
-    return str(a.get("sparse", "")).lower() in ("true", "1")
+_is_sparse = is_sparse
 
 
 def model_table_cfg(job: JobConfig, world_size: int) -> TableConfig:
@@ -115,18 +115,10 @@ def _make_sparse_batches(job: JobConfig, a: dict, rank: int,
         row_ptr, col, val, y = dl.parse_libsvm_csr_split(
             a["input"], rank, world_size, F)
         n_blocks = max(1, job.num_worker_blocks or job.num_mini_batches)
-        n = y.shape[0]
-        # torch.chunk's row ranges, so block i holds the rows the dense
-        # branch would give it
-        size = -(-n // n_blocks) if n else 0
-        blocks = []
-        for lo in range(0, max(1, n), max(1, size)):
-            hi = min(n, lo + size)
-            e0, e1 = int(row_ptr[lo]), int(row_ptr[hi])
-            x = SparseBatch(row_ptr[lo:hi + 1] - e0, col[e0:e1],
-                            val[e0:e1], F)
-            blocks.append((x.to(device), y[lo:hi].to(device)))
-        return blocks, None
+        return [(SparseBatch(*csr, F).to(device), y[lo:hi].to(device))
+                for lo, hi, *csr in csr_row_blocks(row_ptr, col, val,
+                                                   y.shape[0], n_blocks)
+                ], None
     B = int(a["batch_size"])
     k = max(1, min(int(a["nnz_per_row"]), F))
     g = torch.Generator().manual_seed(stable_seed(job.job_id, "data", rank))
@@ -136,16 +128,12 @@ def _make_sparse_batches(job: JobConfig, a: dict, rank: int,
     blocks = []
     n_blocks = job.num_worker_blocks or job.num_mini_batches
     for _ in range(n_blocks):
-        # per-row random feature subset: k draws, sorted, repeats dropped
         cols = torch.randint(0, F, (B, k), generator=g).sort(dim=1).values
-        keep = torch.ones((B, k), dtype=torch.bool)
-        keep[:, 1:] = cols[:, 1:] != cols[:, :-1]
+        keep, row_ptr = drop_repeats(cols)
         vals = torch.randn(B, k, generator=g) * keep
         y = (vals * w_true[cols]).sum(dim=1) \
             + a["noise"] * torch.randn(B, generator=g)
-        row_ptr = torch.zeros(B + 1, dtype=torch.int64)
-        row_ptr[1:] = torch.cumsum(keep.sum(dim=1), 0)
-        x = SparseBatch(row_ptr, cols[keep].to(torch.int32), vals[keep], F)
+        x =SparseBatch(row_ptr, cols[keep].to(torch.int32), vals[keep], F)
         blocks.append((x.to(device), y.to(device)))
     return blocks, w_true
 
@@ -175,15 +163,7 @@ class LassoTrainer(Trainer):
         super().__init__(ctx)
         self.a = defaults(JobConfig(job_id=ctx.job_id, app="lasso",
                                     app_args=ctx.app_args))
-        table = ctx.table(MODEL_TABLE)
-        from harmony_amd.et.onesided import OneSidedTable
-
-        if isinstance(table, OneSidedTable):
-            from harmony_amd.dolphin.model_accessor import OneSidedAccessor
-
-            self.accessor = OneSidedAccessor(table)
-        else:
-            self.accessor = ETModelAccessor(table)
+        self.accessor = accessor_for(ctx.table(MODEL_TABLE))
         self._loss = torch.zeros(())
 
     def pull_model(self) -> None:
@@ -231,30 +211,11 @@ class LassoTrainer(Trainer):
 
 def build(job: JobConfig, ctx, cp):
     cfg = model_table_cfg(job, ctx.world_size)
-    a = defaults(job)
-    if str(a.get("one_sided", "")).lower() in ("true", "1"):
-        from harmony_amd.et.onesided import OneSidedTable
-
-        table = OneSidedTable(cfg, ctx.rank, ctx.world_size, ctx.device,
-                              store=ctx.store)
-        cp.barrier(f"{job.job_id}/os_alloc", ctx.world_size)
-        table.connect()
-        cp.barrier(f"{job.job_id}/os_conn", ctx.world_size)
-    else:
-        comm = ctx.new_data_plane()
-        table = Table(cfg, ctx.rank, ctx.world_size, ctx.device, comm=comm)
+    table = build_ps_table(job, cfg, ctx, cp)
     blocks, _ = make_batches(job, ctx.rank, ctx.device, ctx.world_size)
     tctx = TrainerContext(job_id=job.job_id, rank=ctx.rank,
                           world_size=ctx.world_size, device=ctx.device,
                           tables={MODEL_TABLE: table}, app_args=job.app_args)
     trainer = LassoTrainer(tctx)
-    def _reslice(b, frac):
-        # frac<=0 -> EMPTY batch: a stopped worker (StopWorkerOp) does
-        # zero work and its sparse pulls/pushes carry zero keys
-        n = 0 if frac <= 0 else max(1, int(b[0].shape[0] * frac))
-        if isinstance(b[0], SparseBatch):
-            return (b[0].prefix(n), b[1][:n])
-        return (b[0][:n], b[1][:n])
-
-    provider = TrainingDataProvider(reslice=_reslice, local_blocks=blocks)
+    provider = TrainingDataProvider(reslice=reslice, local_blocks=blocks)
     return {MODEL_TABLE: table}, trainer, provider

@@ -27,9 +27,8 @@ import torch
 
 from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
-from harmony_amd.dolphin.model_accessor import ETModelAccessor
+from harmony_amd.dolphin.model_accessor import accessor_for, build_ps_table
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
-from harmony_amd.et.table import Table
 from harmony_amd.utils import stable_seed
 from harmony_amd import ops
 
@@ -142,17 +141,9 @@ class LDATrainer(Trainer):
         super().__init__(ctx)
         self.a = defaults(JobConfig(job_id=ctx.job_id, app="lda",
                                     app_args=ctx.app_args))
-        table = ctx.table(MODEL_TABLE)
-        from harmony_amd.et.onesided import OneSidedTable
-
-        if isinstance(table, OneSidedTable):
-            # async mode: pulls/pushes are direct xGMI kernels (atomic int
-            # adds); LDA's count algebra is pure add (clamp is a no-op)
-            from harmony_amd.dolphin.model_accessor import OneSidedAccessor
-
-            self.accessor = OneSidedAccessor(table)
-        else:
-            self.accessor = ETModelAccessor(table)
+        # async mode: pulls/pushes are direct xGMI kernels (atomic int
+        # adds); LDA's count algebra is pure add (clamp is a no-op)
+        self.accessor = accessor_for(ctx.table(MODEL_TABLE))
         K = self.a["num_topics"]
         self.doc_topic = torch.zeros(num_local_docs, K, dtype=torch.int32,
                                      device=ctx.device)
@@ -439,19 +430,8 @@ class LDATrainer(Trainer):
 
 
 def build(job: JobConfig, ctx, cp):
-    a = defaults(job)
     cfg = model_table_cfg(job, ctx.world_size)
-    if str(a.get("one_sided", "")).lower() in ("true", "1"):
-        from harmony_amd.et.onesided import OneSidedTable
-
-        table = OneSidedTable(cfg, ctx.rank, ctx.world_size, ctx.device,
-                              store=ctx.store)
-        cp.barrier(f"{job.job_id}/os_alloc", ctx.world_size)
-        table.connect()
-        cp.barrier(f"{job.job_id}/os_conn", ctx.world_size)
-    else:
-        comm = ctx.new_data_plane()
-        table = Table(cfg, ctx.rank, ctx.world_size, ctx.device, comm=comm)
+    table = build_ps_table(job, cfg, ctx, cp)
     blocks, local_docs = make_batches(job, ctx.rank, ctx.device,
                                       ctx.world_size)
     tctx = TrainerContext(job_id=job.job_id, rank=ctx.rank,

@@ -27,10 +27,11 @@ import torch
 
 from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
-from harmony_amd.dolphin.model_accessor import ETModelAccessor
+from harmony_amd.dolphin.model_accessor import accessor_for, build_ps_table
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
-from harmony_amd.et.table import Table
-from harmony_amd.mlapps.sparse_batch import SparseBatch
+from harmony_amd.mlapps.sparse_batch import (SparseBatch, csr_row_blocks,
+                                             drop_repeats, is_sparse,
+                                             reslice)
 from harmony_amd import ops
 
 MODEL_TABLE = "mlr_model"
@@ -44,8 +45,7 @@ def defaults(job: JobConfig) -> dict:
     return a
 
 
-def _is_sparse(a: dict) -> bool:
-    return str(a.get("sparse", "")).lower() in ("true", "1")
+_is_sparse = is_sparse
 
 
 def model_table_cfg(job: JobConfig, world_size: int) -> TableConfig:
@@ -112,16 +112,10 @@ def _make_sparse_batches(job: JobConfig, a: dict, rank: int,
 
         row_ptr, col, val, y = dl.parse_libsvm_csr_split(
             a["input"], rank, world_size, F)
-        n = y.shape[0]
-        # torch.chunk's row ranges, so block i holds the rows the dense
-        # branch would give it
-        size = -(-n // n_blocks) if n else 0
-        for lo in range(0, max(1, n), max(1, size)):
-            hi = min(n, lo + size)
-            e0, e1 = int(row_ptr[lo]), int(row_ptr[hi])
-            x = SparseBatch(row_ptr[lo:hi + 1] - e0, col[e0:e1],
-                            val[e0:e1], F)
-            blocks.append((x.to(device), y[lo:hi].long().to(device)))
+        for lo, hi, *csr in csr_row_blocks(row_ptr, col, val, y.shape[0],
+                                           n_blocks):
+            blocks.append((SparseBatch(*csr, F).to(device),
+                           y[lo:hi].long().to(device)))
         return blocks
     C, B = a["num_classes"], a["batch_size"]
     k = max(1, min(int(a["nnz_per_row"]), F))
@@ -131,13 +125,9 @@ def _make_sparse_batches(job: JobConfig, a: dict, rank: int,
     centers = torch.randn(C, F, generator=g) * 0.5
     for _ in range(n_blocks):
         y = torch.randint(0, C, (B,), generator=g)
-        # per-row random feature subset: k draws, sorted, repeats dropped
         cols = torch.randint(0, F, (B, k), generator=g).sort(dim=1).values
-        keep = torch.ones((B, k), dtype=torch.bool)
-        keep[:, 1:] = cols[:, 1:] != cols[:, :-1]
+        keep, row_ptr = drop_repeats(cols)
         vals = centers[y.unsqueeze(1), cols] + torch.randn(B, k, generator=g)
-        row_ptr = torch.zeros(B + 1, dtype=torch.int64)
-        row_ptr[1:] = torch.cumsum(keep.sum(dim=1), 0)
         x = SparseBatch(row_ptr, cols[keep].to(torch.int32), vals[keep], F)
         blocks.append((x.to(device), y.to(device)))
     return blocks
@@ -148,17 +138,9 @@ class MLRTrainer(Trainer):
         super().__init__(ctx)
         self.a = defaults(JobConfig(job_id=ctx.job_id, app="mlr",
                                     app_args=ctx.app_args))
-        table = ctx.table(MODEL_TABLE)
-        from harmony_amd.et.onesided import OneSidedTable
-
-        if isinstance(table, OneSidedTable):
-            # async mode (app arg one_sided=true): pull/push are direct
-            # xGMI kernels; the worker never issues a collective
-            from harmony_amd.dolphin.model_accessor import OneSidedAccessor
-
-            self.accessor = OneSidedAccessor(table)
-        else:
-            self.accessor = ETModelAccessor(table)
+        # async mode (app arg one_sided=true): pull/push are direct xGMI
+        # kernels; the worker never issues a collective
+        self.accessor = accessor_for(ctx.table(MODEL_TABLE))
         self.step_size = self.a["step_size"]
         self.W = None          # [C*P, F/P] pulled model
         # hipGraph capture of the compute phase (static per block); the
@@ -301,32 +283,11 @@ class MLRTrainer(Trainer):
 
 def build(job: JobConfig, ctx, cp):
     cfg = model_table_cfg(job, ctx.world_size)
-    a = defaults(job)
-    if str(a.get("one_sided", "")).lower() in ("true", "1"):
-        # async PS mode: hipIpc/xGMI one-sided table — no collectives in
-        # the training loop, SSP slack is the only cross-worker coupling
-        from harmony_amd.et.onesided import OneSidedTable
-
-        table = OneSidedTable(cfg, ctx.rank, ctx.world_size, ctx.device,
-                              store=ctx.store)
-        cp.barrier(f"{job.job_id}/os_alloc", ctx.world_size)
-        table.connect()
-        cp.barrier(f"{job.job_id}/os_conn", ctx.world_size)
-    else:
-        comm = ctx.new_data_plane()
-        table = Table(cfg, ctx.rank, ctx.world_size, ctx.device, comm=comm)
+    table = build_ps_table(job, cfg, ctx, cp)
     tctx = TrainerContext(job_id=job.job_id, rank=ctx.rank,
                           world_size=ctx.world_size, device=ctx.device,
                           tables={MODEL_TABLE: table}, app_args=job.app_args)
     trainer = MLRTrainer(tctx)
-    def _reslice(b, frac):
-        # frac<=0 -> EMPTY batch: a stopped worker (StopWorkerOp) does
-        # zero work and its sparse pulls/pushes carry zero keys
-        n = 0 if frac <= 0 else max(1, int(b[0].shape[0] * frac))
-        if isinstance(b[0], SparseBatch):
-            return (b[0].prefix(n), b[1][:n])
-        return (b[0][:n], b[1][:n])
-
-    provider = TrainingDataProvider(reslice=_reslice, local_blocks=
+    provider = TrainingDataProvider(reslice=reslice, local_blocks=
         make_batches(job, ctx.rank, ctx.device, ctx.world_size))
     return {MODEL_TABLE: table}, trainer, provider

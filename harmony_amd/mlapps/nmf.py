@@ -23,9 +23,8 @@ import torch
 
 from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
-from harmony_amd.dolphin.model_accessor import ETModelAccessor
+from harmony_amd.dolphin.model_accessor import accessor_for, build_ps_table
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
-from harmony_amd.et.table import Table
 from harmony_amd.utils import stable_seed
 from harmony_amd import ops
 
@@ -149,19 +148,11 @@ class NMFTrainer(Trainer):
         super().__init__(ctx)
         self.a = defaults(JobConfig(job_id=ctx.job_id, app="nmf",
                                     app_args=ctx.app_args))
-        table = ctx.table(MODEL_TABLE)
-        from harmony_amd.et.onesided import OneSidedTable
-
-        if isinstance(table, OneSidedTable):
-            # async mode (one_sided=true): pulls are xGMI gather kernels;
-            # pushes go through the owner-side apply-queue RINGS (v2) since
-            # nmf_sgd is not add-algebra — reference per-block op-queue
-            # semantics (CommManager.java:36-155)
-            from harmony_amd.dolphin.model_accessor import OneSidedAccessor
-
-            self.accessor = OneSidedAccessor(table)
-        else:
-            self.accessor = ETModelAccessor(table)
+        # async mode (one_sided=true): pulls are xGMI gather kernels;
+        # pushes go through the owner-side apply-queue RINGS (v2) since
+        # nmf_sgd is not add-algebra — reference per-block op-queue
+        # semantics (CommManager.java:36-155)
+        self.accessor = accessor_for(ctx.table(MODEL_TABLE))
         # Worker-local model table (reference: local table rowKey -> L row,
         # DolphinJobEntity.java:100-110): device-resident, never leaves HBM.
         g = torch.Generator().manual_seed(stable_seed(ctx.job_id, "L", ctx.rank))
@@ -275,18 +266,7 @@ class NMFTrainer(Trainer):
 
 def build(job: JobConfig, ctx, cp):
     cfg = model_table_cfg(job, ctx.world_size)
-    a = defaults(job)
-    if str(a.get("one_sided", "")).lower() in ("true", "1"):
-        from harmony_amd.et.onesided import OneSidedTable
-
-        table = OneSidedTable(cfg, ctx.rank, ctx.world_size, ctx.device,
-                              store=ctx.store)
-        cp.barrier(f"{job.job_id}/os_alloc", ctx.world_size)
-        table.connect()
-        cp.barrier(f"{job.job_id}/os_conn", ctx.world_size)
-    else:
-        comm = ctx.new_data_plane()
-        table = Table(cfg, ctx.rank, ctx.world_size, ctx.device, comm=comm)
+    table = build_ps_table(job, cfg, ctx, cp)
     blocks, rows_local = make_batches(job, ctx.rank, ctx.device,
                                       ctx.world_size)
     tctx = TrainerContext(job_id=job.job_id, rank=ctx.rank,

@@ -2,8 +2,8 @@
 two launches) against the torch path of the same op on the same GPU, at
 n_nodes in {1, 8, 64}, F in {32, 784}, nb = 64, all-continuous and
 half-categorical types; and a whole tree build through K10b (build_tree with
-all-zero feature types) against the untyped build_tree (the tensor-op search
-with its three host syncs per level) on the same batch. Runs are interleaved
+all-zero feature types) against the untyped build_tree (the tensor-op search;
+both make one host copy per level) on the same batch. Runs are interleaved
 round by round; each figure is the median over rounds of a per-round median,
 with the min..max over rounds.
 
@@ -141,7 +141,7 @@ def build_ab():
          "nb = 64, lam = 1.")
     emit()
     emit("| F | max_depth | typed (K10 + K10b, one copy per level) | "
-         "untyped (tensor ops, three syncs per level) | untyped / typed | "
+         "untyped (tensor ops, one copy per level) | untyped / typed | "
          "typed against untyped tree |")
     emit("|---|---|---|---|---|---|")
     for F in (32, 784):
