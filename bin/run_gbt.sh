@@ -2,5 +2,8 @@
 # Standalone gbt run without the job server (reference run_gbt.sh /
 # ETDolphinLauncher mode). Multi-GPU: wrap with torchrun (see
 # harmony_amd/standalone.py).
+# -test_data_path <file> (with or without file://): a held-out file in the
+# -input format, read whole by every rank before training; the summary then
+# holds test_mse or test_error_rate and test_examples.
 cd "$(dirname "$0")/.."
 exec python -m harmony_amd.standalone -app gbt "$@"

@@ -98,6 +98,15 @@ def run_job(job: JobConfig, ctx: ExecutorContext,
     cp = cp or ControlPlane(ctx.store, ctx.rank, ctx.world_size)
     tus = tus or TaskUnitScheduler(cp, {job.job_id}, multi_job=False)
     app = mlapps.get_app(job.app)
+    from harmony_amd.mlapps import heldout
+
+    if heldout.test_path(job.app_args) and \
+            job.app not in heldout.SUPPORTED_APPS:
+        from harmony_amd.utils.joblog import job_logger
+
+        job_logger(job.job_id, ctx.rank).info(
+            "test_data_path is ignored: app %s has no test evaluation",
+            job.app)
     tables, trainer, provider = app.build(job, ctx, cp)
     if job.restore_chkp:
         _restore_tables(job, tables)
@@ -169,7 +178,10 @@ def run_job(job: JobConfig, ctx: ExecutorContext,
 
     with _eval_net(_EVAL_PHASE):
         ev = trainer.evaluate_model()
-    for k, v in (ev or {}).items():
+        # held-out test data (app arg test_data_path): MLR and Lasso pull
+        # the model here, a collective, so every rank calls it
+        tv = trainer.evaluate_test()
+    for k, v in {**(ev or {}), **(tv or {})}.items():
         metrics.add_custom(k, float(v))
     if job.offline_model_eval and chkp_mgr is not None:
         from harmony_amd.dolphin.model_eval import ModelEvaluator

@@ -40,7 +40,8 @@ class ModelChkpManager:
 
 class ModelEvaluator:
     """Replays checkpoints: for each epoch snapshot, restore the model tables
-    and run trainer.evaluate_model() over the training data."""
+    and run trainer.evaluate_model() over the training data, then
+    trainer.evaluate_test() over the held-out test data (test_* keys)."""
 
     def __init__(self, cm: CheckpointManager, app_id: str, tables: dict,
                  trainer, provider):
@@ -62,7 +63,10 @@ class ModelEvaluator:
                 self.trainer.set_batch_data(batch)
                 self.trainer.pull_model()
                 self.trainer.local_compute()
-            out[cid] = self.trainer.evaluate_model() or {}
+            res = dict(self.trainer.evaluate_model() or {})
+            # the checkpoint on the held-out test data, if the job has any
+            res.update(self.trainer.evaluate_test() or {})
+            out[cid] = res
         return out
 
 

@@ -35,6 +35,9 @@ class Trainer:
 
     def __init__(self, ctx: TrainerContext):
         self.ctx = ctx
+        # held-out test blocks (app arg test_data_path), set by the app's
+        # build(); empty when the job has no test data
+        self.test_blocks: list = []
 
     def initialize(self) -> None:
         """Once per tasklet before the first epoch (initGlobalSettings)."""
@@ -57,6 +60,14 @@ class Trainer:
 
     def evaluate_model(self) -> Dict[str, float]:
         """Offline model evaluation (reference ModelEvaluator)."""
+        return {}
+
+    def evaluate_test(self) -> Dict[str, float]:
+        """The current model on the trainer's held-out test blocks
+        (reference Trainer.evaluateModel(trainingData, testData)): test_*
+        metrics, {} when there are none. Called on every rank (it may pull
+        the model, a collective); it must leave the training state and what
+        evaluate_model() reports unchanged."""
         return {}
 
     def cleanup(self) -> None:

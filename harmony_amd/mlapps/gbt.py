@@ -18,7 +18,7 @@ stored in an object table keyed by label (multi-class = one forest per
 label, regression = label 0).
 
 App args: num_features, batch_size, num_bins, max_depth, step_size
-(shrinkage), lam (leaf L2), objective ("regression" | "multiclass"
+(shrinkage), lam (leaf L2), test_data_path, objective ("regression" | "multiclass"
 with num_classes — one forest per label in the object table, reference
 GBTTrainer's valueTypeNum > 3 path / GroupedTree).
 
@@ -39,6 +39,18 @@ quantize gives the densified block, the level histograms come from K10s
 and prediction look a bin up instead of gathering it from a dense row. On
 the same data the trees equal the dense path's; memory and time follow nnz
 and the number of present features, never B * F.
+
+test_data_path (mlapps/heldout.py; reference TestDataProvider): a held-out
+file, read whole by every rank in build() and kept as ONE block, binned
+exactly as a training block is (quantize / SparseBins with the job's feature
+types, the same ValueError for a bad category). evaluate_test() applies the
+whole forest to it with gbt.forest_predict (K10p, ops.gbt_forest_predict) and
+reports test_mse (regression) or test_error_rate (multiclass) with
+test_examples. Binning semantics: a tree here stores BIN INDICES, and every
+block is binned by its own quantiles, so the forest is applied to the test
+set's own quantile bins, the same way it is applied to every training block.
+Job-wide bin edges stored with the model would change training results and
+are not built (docs/ROADMAP.md).
 """
 
 from __future__ import annotations
@@ -52,6 +64,7 @@ from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
 from harmony_amd.et.table import ObjectTable
+from harmony_amd.mlapps import heldout
 from harmony_amd.mlapps.sparse_batch import (csr_row_blocks, drop_repeats,
                                              is_sparse, reslice)
 from harmony_amd.mlapps.sparse_bins import SparseBins
@@ -178,6 +191,52 @@ def decode_trees(enc, depth: int):
         out.append((key, GBTree(depth=depth, feature=feat, threshold=thr,
                                 leaf_value=lv, cat_mask=masks)))
     return out
+
+
+def pack_forest(forest: List[GBTree], depth: int) -> torch.Tensor:
+    """The device format of a forest: the int32 [T, row] tensor
+    encode_trees gives for [(0, tree), ...] (key word 0), one row per tree in
+    forest order. Built column block by column block, one host tensor per
+    block instead of encode_trees' four to six per tree (about a tenth of
+    its time at 1024 trees; tests/test_gbt_predict_cpu.py holds the two
+    equal)."""
+    if not forest:
+        return encode_trees([], depth)
+    ni = (1 << depth) - 1
+    assert all(t.depth == depth for t in forest)
+    parts = [
+        torch.tensor([[0] + t.feature + t.threshold for t in forest],
+                     dtype=torch.int32),
+        torch.tensor([t.leaf_value for t in forest],
+                     dtype=torch.float32).view(torch.int32)]
+    if any(t.cat_mask is not None for t in forest):
+        m = torch.tensor([t.cat_mask if t.cat_mask is not None else [0] * ni
+                          for t in forest], dtype=torch.int64)
+        halves = m.view(torch.int32).view(len(forest), ni, 2)  # little-endian
+        parts += [halves[:, :, 0], halves[:, :, 1]]
+    return torch.cat(parts, dim=1).contiguous()
+
+
+# Trees from which forest_predict packs the forest and runs K10p; below it
+# the per-tree predict_bins loop stays. Measured (profiles/gbt_predict_ab.md):
+# K10p with its pack time wins from a single tree on, dense and sparse.
+FOREST_KERNEL_MIN_TREES = 1
+
+
+def forest_predict(forest: List[GBTree], bins, step_size: float
+                   ) -> torch.Tensor:
+    """step_size * the forest's prediction for dense bins or a SparseBins,
+    float32 [B]: what GBTTrainer._forest_pred gives from an empty cache, bit
+    for bit, in one launch on the device (ops.gbt_forest_predict)."""
+    if len(forest) < max(1, FOREST_KERNEL_MIN_TREES):
+        pred = torch.zeros(bins.shape[0], dtype=torch.float32,
+                           device=bins.device)
+        for t in forest:
+            pred = pred + step_size * t.predict_bins(bins)
+        return pred
+    depth = forest[0].depth
+    return ops.gbt_forest_predict(bins, pack_forest(forest, depth), depth,
+                                  step_size)
 
 
 MAX_CATEGORIES = 64    # a node's categories are one 64-bit mask
@@ -501,6 +560,27 @@ class GBTTrainer(Trainer):
             return {"error_rate": self._mse, "num_trees": n}
         return {"mse": self._mse, "num_trees": float(len(self.forest))}
 
+    def evaluate_test(self):
+        """The current forest on the held-out block: one forest_predict per
+        forest. Training state (_mse, the prediction caches) is not
+        touched; pull_model only refreshes the replica, as the next batch
+        would."""
+        if not self.test_blocks:
+            return {}
+        self.pull_model()
+        bins, y = self.test_blocks[0]
+        step = self.a["step_size"]
+        out = {"test_examples": float(y.shape[0])}
+        if self.a["objective"] == "multiclass":
+            scores = [forest_predict(f, bins, step) for f in self.forests]
+            pred_cls = torch.stack(scores, dim=1).argmax(dim=1)
+            out["test_error_rate"] = float(
+                (pred_cls != y.long()).float().mean())
+        else:
+            resid = y - forest_predict(self.forest, bins, step)
+            out["test_mse"] = float((resid * resid).mean())
+        return out
+
     def num_batch_examples(self) -> int:
         return self.batch[0].shape[0]
 
@@ -642,7 +722,28 @@ def make_batches(job: JobConfig, rank: int, device: torch.device,
     return blocks
 
 
+def make_test_block(job: JobConfig, device: torch.device):
+    """The held-out file of test_data_path as ONE (bins, y) block, binned as
+    a training block is; [] without the arg. Every rank reads the whole
+    file."""
+    a = defaults(job)
+    path = heldout.test_path(a)
+    if path is None:
+        return []
+    F, nb = int(a["num_features"]), int(a["num_bins"])
+    ftypes = feature_types(a)
+    if _is_sparse(a):
+        row_ptr, col, val, y = heldout.load_rows(path, F, True)
+        x = SparseBins((row_ptr, col, val, F), nb, ftypes)
+    else:
+        X, y = heldout.load_rows(path, F, False)
+        x = quantize(X, nb, ftypes)
+    return [(x.to(device), y.float().to(device))]
+
+
 def build(job: JobConfig, ctx, cp):
+    # before anything else: a missing test file fails the job at once
+    test_blocks = make_test_block(job, ctx.device)
     cfg = TableConfig(table_id=f"{job.job_id}/{MODEL_TABLE}", num_keys=16,
                       num_blocks=16, storage="object")
     comm = ctx.new_data_plane()
@@ -653,6 +754,7 @@ def build(job: JobConfig, ctx, cp):
                           world_size=ctx.world_size, device=ctx.device,
                           tables={MODEL_TABLE: table}, app_args=job.app_args)
     trainer = GBTTrainer(tctx)
+    trainer.test_blocks = test_blocks
     provider = TrainingDataProvider(reslice=reslice, local_blocks=
         make_batches(job, ctx.rank, ctx.device, ctx.world_size))
     return {MODEL_TABLE: table}, trainer, provider

@@ -13,7 +13,10 @@ batch; the full sweep stays on the GPU (F small relative to batch).
 
 App args: num_features, num_parts, batch_size, lam, step_size(unused),
 noise, density; sparse (default false) and nnz_per_row (synthetic sparse
-generator, default 32).
+generator, default 32); test_data_path (mlapps/heldout.py; reference
+TestDataProvider): a held-out file read whole by every rank in build(), cut
+into blocks of at most batch_size rows; evaluate_test() reports test_mse and
+test_examples for the final model and for every offline checkpoint.
 
 sparse=true keeps every batch as a SparseBatch (CSR + static column index),
 as the reference does (LassoETParser createSparse, horzcatVecSparse at
@@ -39,6 +42,7 @@ from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
 from harmony_amd.dolphin.model_accessor import accessor_for, build_ps_table
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
+from harmony_amd.mlapps import heldout
 from harmony_amd.mlapps.sparse_batch import (SparseBatch, csr_row_blocks,
                                              drop_repeats, is_sparse,
                                              reslice)
@@ -205,11 +209,42 @@ class LassoTrainer(Trainer):
     def evaluate_model(self):
         return {"mse": float(self._loss)}
 
+    def evaluate_test(self):
+        """test_mse of y - Xw over the held-out blocks, for the model as
+        pulled now (a collective). Nothing of the training state (self.w,
+        _loss) is touched. The squared residuals are summed in fp64 over all
+        blocks and divided once."""
+        if not self.test_blocks:
+            return {}
+        w = self.accessor.pull_all()[:self.a["num_parts"]].reshape(-1)
+        sq = torch.zeros((), dtype=torch.float64, device=w.device)
+        n = 0
+        for X, y in self.test_blocks:
+            if isinstance(X, SparseBatch):
+                # follow the non-zeros: a row's sum in fp64, rounded once to
+                # fp32, so the order of the device's atomic index_add_ does
+                # not show in the value (as in _sparse_col_sq)
+                B = X.shape[0]
+                row = torch.repeat_interleave(
+                    torch.arange(B, device=X.device),
+                    X.row_ptr[1:] - X.row_ptr[:-1])
+                xw = torch.zeros(B, dtype=torch.float64, device=X.device)
+                xw.index_add_(0, row,
+                              X.val.double() * w.double()[X.col.long()])
+                r = y - xw.float()
+            else:
+                r = y - X @ w
+            sq += (r.double() * r.double()).sum()
+            n += y.shape[0]
+        return {"test_mse": float(sq) / n, "test_examples": float(n)}
+
     def num_batch_examples(self) -> int:
         return self.batch[0].shape[0]
 
 
 def build(job: JobConfig, ctx, cp):
+    # before anything else: a missing test file fails the job at once
+    test_blocks = heldout.row_blocks(defaults(job), ctx.device)
     cfg = model_table_cfg(job, ctx.world_size)
     table = build_ps_table(job, cfg, ctx, cp)
     blocks, _ = make_batches(job, ctx.rank, ctx.device, ctx.world_size)
@@ -217,5 +252,6 @@ def build(job: JobConfig, ctx, cp):
                           world_size=ctx.world_size, device=ctx.device,
                           tables={MODEL_TABLE: table}, app_args=job.app_args)
     trainer = LassoTrainer(tctx)
+    trainer.test_blocks = test_blocks
     provider = TrainingDataProvider(reslice=reslice, local_blocks=blocks)
     return {MODEL_TABLE: table}, trainer, provider

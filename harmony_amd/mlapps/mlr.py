@@ -18,7 +18,11 @@ step_size, lambda (L2), dtype; sparse (default false) keeps every batch as a
 SparseBatch (CSR + static column index) and runs the K4s gather-reduce
 kernels (ops/csrc/mlr_sparse.hip) instead of the dense GEMM pair, so the
 input's feature space may be far wider than a row is long; nnz_per_row sizes
-the synthetic sparse generator.
+the synthetic sparse generator; test_data_path (mlapps/heldout.py; reference
+TestDataProvider): a held-out file read whole by every rank in build(), cut
+into blocks of at most batch_size rows; evaluate_test() reports
+test_cross_entropy, test_accuracy and test_examples for the final model and
+for every offline checkpoint.
 """
 
 from __future__ import annotations
@@ -29,6 +33,7 @@ from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
 from harmony_amd.dolphin.model_accessor import accessor_for, build_ps_table
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
+from harmony_amd.mlapps import heldout
 from harmony_amd.mlapps.sparse_batch import (SparseBatch, csr_row_blocks,
                                              drop_repeats, is_sparse,
                                              reslice)
@@ -277,17 +282,49 @@ class MLRTrainer(Trainer):
         self._loss_n = 0
         return out
 
+    def evaluate_test(self):
+        """Cross entropy and accuracy of the model as pulled now (a
+        collective) on the held-out blocks, by the forward kernels alone:
+        loss and correct counts are summed over the blocks and divided
+        once. The pulled model stays local, so W, the accumulators of
+        evaluate_model() and the graph buffers are untouched."""
+        if not self.test_blocks:
+            return {}
+        C, P = self.a["num_classes"], self.a["num_parts_per_class"]
+        W = self.accessor.pull_all()[:C * P].reshape(
+            C, self.a["num_features"])
+        loss = torch.zeros((), dtype=torch.float64, device=W.device)
+        correct = torch.zeros((), dtype=torch.int64, device=W.device)
+        n = 0
+        for x, y in self.test_blocks:
+            if isinstance(x, SparseBatch):
+                _p, l, c = ops.mlr_sparse_forward(
+                    x.row_ptr, x.col, x.val, W, y,
+                    Wt_buf=self._sparse_wt_buf())
+            else:
+                _p, l, c = ops.mlr_forward(x, W, y)
+            loss += l
+            correct += c
+            n += x.shape[0]
+        return {"test_cross_entropy": float(loss) / n,
+                "test_accuracy": float(correct) / n,
+                "test_examples": float(n)}
+
     def num_batch_examples(self) -> int:
         return self.batch[0].shape[0]
 
 
 def build(job: JobConfig, ctx, cp):
+    # before anything else: a missing test file fails the job at once
+    test_blocks = heldout.row_blocks(defaults(job), ctx.device,
+                                     label_dtype=torch.int64)
     cfg = model_table_cfg(job, ctx.world_size)
     table = build_ps_table(job, cfg, ctx, cp)
     tctx = TrainerContext(job_id=job.job_id, rank=ctx.rank,
                           world_size=ctx.world_size, device=ctx.device,
                           tables={MODEL_TABLE: table}, app_args=job.app_args)
     trainer = MLRTrainer(tctx)
+    trainer.test_blocks = test_blocks
     provider = TrainingDataProvider(reslice=reslice, local_blocks=
         make_batches(job, ctx.rank, ctx.device, ctx.world_size))
     return {MODEL_TABLE: table}, trainer, provider

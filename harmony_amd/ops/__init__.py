@@ -18,6 +18,7 @@ Kernel inventory (reference hot loops):
   K10 gbt_hist            GBTTrainer.java:244+ (histogram method)
   K10b gbt_best_split     GBTTrainer.java bestSplitRealFeature/LabelFeature
   K10s gbt_hist_sparse    K10 over SparseVector samples (GBTETDataParser)
+  K10p gbt_forest_predict GBTTrainer.java predictByTree over the whole forest
   K11 lasso_cd            LassoTrainer.java:164-190
   K11s lasso_cd_sparse    LassoTrainer.java:164-208 over SparseVector columns
   K12 loss reductions     NMFTrainer.java:414-456 etc.
@@ -1018,6 +1019,97 @@ def gbt_best_split(cnt: torch.Tensor, s: torch.Tensor, ftype: torch.Tensor,
                         torch.where(split, bp, zero - 1)).to(torch.int32),
             torch.where(wcat, mask, zero),
             torch.where(split, best_gain, torch.zeros_like(best_gain)))
+
+
+GBT_PREDICT_MAX_DEPTH = 8       # K10p: deeper trees take the torch loop
+GBT_PREDICT_LDS_WORDS = 8192    # K10p: words of staged trees per LDS group
+
+
+def gbt_predict_group_trees(row_len: int) -> int:
+    """Trees K10p stages in LDS at a time, for rows of row_len words as the
+    kernel sees them (a SparseBins batch adds 2^d - 1 words to a row)."""
+    return GBT_PREDICT_LDS_WORDS // row_len
+
+
+def gbt_forest_check(forest: torch.Tensor, depth: int, num_features: int
+                     ) -> torch.Tensor:
+    """The host copy of a packed forest (gbt.encode_trees), checked: int32
+    [T, row] with a row length that fits `depth` (with or without the mask
+    words) and every feature index in 0 .. num_features - 1, else
+    ValueError. A restored forest may come from a job with another F; it
+    must never become an out-of-bounds read."""
+    ni = (1 << depth) - 1
+    base = 1 + 2 * ni + (1 << depth)
+    host = forest.cpu()
+    if host.dim() != 2 or host.dtype != torch.int32 or \
+            host.shape[1] not in (base, base + 2 * ni):
+        raise ValueError(
+            f"packed forest {tuple(host.shape)} {host.dtype}: a depth-"
+            f"{depth} row has {base} or {base + 2 * ni} int32 words")
+    feat = host[:, 1:1 + ni]
+    if feat.numel() and (int(feat.min()) < 0
+                         or int(feat.max()) >= num_features):
+        raise ValueError(
+            f"packed forest: feature index {int(feat.min())}.."
+            f"{int(feat.max())} outside 0..{num_features - 1}")
+    return host
+
+
+def gbt_forest_predict(bins, forest: torch.Tensor, depth: int,
+                       step_size: float) -> torch.Tensor:
+    """step_size * the prediction of a packed forest for binned rows (K10p,
+    ops/csrc/gbt_predict.hip): float32 [B]. bins: dense int64 [B, F] bins or
+    a mlapps.sparse_bins.SparseBins; forest: the int32 [T, row] tensor of
+    gbt.encode_trees, on any device (it is checked on the host by
+    gbt_forest_check before anything is launched, then copied once).
+
+    Formula, GBTTrainer._forest_pred from an empty cache: pred = 0, then for
+    each tree in forest order pred = pred + fp32(step_size) * leaf, one
+    rounded multiply and one rounded add per tree; the leaf is found by
+    gbt._route_right per level. A SparseBins row uses SparseBins.bin_of.
+
+    CPU tensors, HARMONY_FORCE_TORCH_OPS=1 and depth > 8 take the torch loop
+    below (GBTree.predict_bins per tree), which is the kernel's test oracle;
+    the kernel's result is bit-identical to it."""
+    from harmony_amd.mlapps.sparse_bins import SparseBins
+
+    B, F = bins.shape
+    dev = bins.device
+    host = gbt_forest_check(forest, depth, F)
+    T = host.shape[0]
+    if not (_use_hip(bins.keys if isinstance(bins, SparseBins) else bins)
+            and depth <= GBT_PREDICT_MAX_DEPTH):
+        from harmony_amd.mlapps.gbt import decode_trees
+
+        pred = torch.zeros(B, dtype=torch.float32, device=dev)
+        for _key, tree in decode_trees(host, depth):
+            pred = pred + step_size * tree.predict_bins(bins)
+        return pred
+    if B == 0 or T == 0:
+        return torch.zeros(B, dtype=torch.float32, device=dev)
+    packed = host.to(dev)
+    if not isinstance(bins, SparseBins):
+        return _hip.gbt_forest_predict(
+            bins.long().contiguous(), packed, int(depth), float(step_size),
+            int(F), None, None, None)
+    # per (tree, node), independent of the row: the zero bin of the node's
+    # feature, 0 for a feature absent from the batch (SparseBins.bin_of)
+    ni = (1 << depth) - 1
+    feat = packed[:, 1:1 + ni].long()
+    ids = bins.feat_ids.long()
+    nf = ids.shape[0]
+    if nf:
+        k = torch.searchsorted(ids, feat).clamp_(max=nf - 1)
+        zb = torch.where(ids[k] == feat, bins.zero_bin[k],
+                         torch.zeros_like(bins.zero_bin[k]))
+    else:
+        zb = torch.zeros_like(feat, dtype=torch.int32)
+    row_ptr = torch.searchsorted(
+        bins.keys, torch.arange(B + 1, dtype=torch.int64, device=dev) * F)
+    return _hip.gbt_forest_predict(
+        None, torch.cat([packed, zb.to(torch.int32)], dim=1).contiguous(),
+        int(depth), float(step_size), int(F), bins.keys.contiguous(),
+        bins.key_bin.contiguous(), row_ptr)
 
 
 def lasso_cd(X: torch.Tensor, r: torch.Tensor, w: torch.Tensor,

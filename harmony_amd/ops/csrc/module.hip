@@ -112,6 +112,13 @@ std::vector<torch::Tensor> gbt_hist_sparse(
     torch::Tensor node, torch::Tensor node_cnt, torch::Tensor node_sum,
     int64_t nb);
 int64_t gbt_hist_sparse_max_cells();
+torch::Tensor gbt_forest_predict(
+    c10::optional<torch::Tensor> bins, torch::Tensor forest, int64_t depth,
+    double step_size, int64_t F, c10::optional<torch::Tensor> keys,
+    c10::optional<torch::Tensor> key_bin,
+    c10::optional<torch::Tensor> row_ptr);
+int64_t gbt_predict_max_depth();
+int64_t gbt_predict_lds_words();
 void scatter_apply(torch::Tensor shard, torch::Tensor rows,
                    torch::Tensor deltas, int64_t mode, double step,
                    double maxval);
@@ -176,6 +183,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "GBT level histogram over a SparseBins column index (K10s)");
   m.def("gbt_hist_sparse_max_cells", &gbt_hist_sparse_max_cells,
         "widest level (n_nodes * nb) K10s keeps in LDS");
+  m.def("gbt_forest_predict", &gbt_forest_predict,
+        "GBT packed forest applied to dense or sparse bins (K10p)");
+  m.def("gbt_predict_max_depth", &gbt_predict_max_depth,
+        "deepest tree K10p takes");
+  m.def("gbt_predict_lds_words", &gbt_predict_lds_words,
+        "words of staged trees per LDS group of K10p");
   m.def("lasso_cd", &lasso_cd, "Lasso persistent CD sweep (K11)");
   m.def("lasso_cd_sparse", &lasso_cd_sparse,
         "Lasso CD sweep over a batch's column index (K11s)");
