@@ -23,6 +23,8 @@ Kernel inventory (reference hot loops):
   K11s lasso_cd_sparse    LassoTrainer.java:164-208 over SparseVector columns
   K12 loss reductions     NMFTrainer.java:414-456 etc.
   K13 pregel_pull         pregel MessageManager.addMessage + MessageCombiner
+  K13p pregel_push        K13 along the out-edges of the sending vertices only
+                          (ComputationCallable.java:36 runs woken vertices)
 """
 
 from __future__ import annotations
@@ -1322,6 +1324,100 @@ def pregel_pull(in_ptr: torch.Tensor, in_src: torch.Tensor,
     else:
         out = torch.zeros(R, dtype=vert_msg.dtype, device=dev)
         out.index_add_(0, row, v)
+    return out, flag
+
+
+# ---------------------------------------------------------------------------
+# K13p: Pregel push (send + combine along the frontier's out-edges)
+# ---------------------------------------------------------------------------
+
+def pregel_push(out_ptr: torch.Tensor, out_row: torch.Tensor,
+                out_w: Optional[torch.Tensor], w_const: float,
+                vert_msg: torch.Tensor, frontier: torch.Tensor,
+                num_rows: int, combiner: str, add_weight: bool,
+                send_mask: Optional[torch.Tensor] = None,
+                _edges_hint: int = -1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One superstep's message send + combine along the out-edges of the
+    sending vertices only (K13p, ops/csrc/pregel_push.hip): pregel_pull's
+    result at the cost of the frontier's edges instead of the whole index.
+
+    The local out-CSR in original edge order: out_ptr int64 [n_local+1],
+    out_row int32 [E], out_w float32 [E] or None. out_row[e] is the
+    destination ROW in the pull index's row space (0..n_local-1 local
+    vertices, n_local + position in remote_keys for remote ones; see
+    pregel.engine.build_push_index). frontier int32 [nf]: local indices of
+    the sending vertices; a repeated entry is harmless (min is idempotent).
+    send_mask (uint8/bool [n_local], optional) narrows the frontier to the
+    entries whose vertex it marks: a caller that holds a mask on the device
+    passes frontier = all vertices with it and needs neither a compaction
+    nor a host read of the frontier's size.
+
+    out[r] = min over the edges e of frontier vertices that end in row r of
+    vert_msg[src] (+ out_w[e], or w_const when out_w is None, if
+    add_weight), each one rounded float32 add as in K13; +inf when there is
+    none. flag[r] = 1 iff at least one such edge exists (even when its value
+    is +inf). So the result equals pregel_pull on the inverted index with
+    send_mask = the indicator of frontier, value for value.
+    Returns (out float32 [num_rows], flag uint8 [num_rows]).
+
+    combiner must be "min": the kernel combines with integer atomics on the
+    float's bits, whose result does not depend on arrival order; "add" would
+    need float atomic adds and lose K13's bitwise reproducibility, and
+    raises ValueError. NaN messages are unspecified (K13's fminf drops
+    them). A frontier id outside [0, n_local) and a row outside
+    [0, num_rows) are skipped, edge ranges are clamped to [0, E]; nf == 0 or
+    num_rows == 0 launches nothing.
+
+    CPU tensors (and HARMONY_FORCE_TORCH_OPS=1) take the torch reference
+    below (a scatter_reduce_ amin over the frontier's edges), which is also
+    the kernel's test oracle. _edges_hint: the caller's count of frontier
+    edges, if it has one; it only sizes the kernel's grid."""
+    if combiner != "min":
+        raise ValueError(
+            f"pregel_push supports the min combiner only, got {combiner!r}: "
+            "a pushed add needs float atomics, whose sum depends on arrival "
+            "order")
+    R = int(num_rows)
+    if _use_hip(vert_msg):
+        mask = None
+        if send_mask is not None:
+            mask = (send_mask.view(torch.uint8)
+                    if send_mask.dtype == torch.bool
+                    else send_mask.to(torch.uint8)).contiguous()
+        out, flag = _hip.pregel_push(
+            out_ptr.contiguous(), out_row.contiguous(),
+            None if out_w is None else out_w.contiguous(), float(w_const),
+            vert_msg.contiguous(), frontier.to(torch.int32).contiguous(),
+            mask, R, bool(add_weight), int(_edges_hint))
+        return out, flag
+    dev = vert_msg.device
+    n_local = out_ptr.shape[0] - 1
+    n_edges = out_row.shape[0]
+    out = torch.full((R,), float("inf"), dtype=torch.float32, device=dev)
+    flag = torch.zeros(R, dtype=torch.uint8, device=dev)
+    f = frontier.long()
+    f = f[(f >= 0) & (f < n_local)]
+    if send_mask is not None:
+        f = f[send_mask.bool()[f]]
+    if f.numel() == 0 or R == 0:
+        return out, flag
+    beg = out_ptr[f].clamp(0, n_edges)
+    end = out_ptr[f + 1].clamp(0, n_edges)
+    cnt = (end - beg).clamp_min(0)
+    fptr = torch.cumsum(cnt, 0) - cnt
+    total = int(cnt.sum())
+    src = torch.repeat_interleave(f, cnt)
+    e = (torch.arange(total, device=dev)
+         - torch.repeat_interleave(fptr, cnt)
+         + torch.repeat_interleave(beg, cnt))
+    row = out_row[e].long()
+    v = vert_msg[src].float()
+    if add_weight:
+        v = v + (out_w[e] if out_w is not None else w_const)
+    ok = (row >= 0) & (row < R)
+    row, v = row[ok], v[ok]
+    flag[row] = 1
+    out.scatter_reduce_(0, row, v, reduce="amin", include_self=True)
     return out, flag
 
 

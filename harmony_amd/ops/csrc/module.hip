@@ -137,6 +137,12 @@ std::vector<torch::Tensor> pregel_pull(
     c10::optional<torch::Tensor> in_w, double w_const, torch::Tensor vert_msg,
     c10::optional<torch::Tensor> send_mask, int64_t combiner, bool add_weight,
     int64_t group);
+std::vector<torch::Tensor> pregel_push(
+    torch::Tensor out_ptr, torch::Tensor out_row,
+    c10::optional<torch::Tensor> out_w, double w_const,
+    torch::Tensor vert_msg, torch::Tensor frontier,
+    c10::optional<torch::Tensor> send_mask, int64_t num_rows,
+    bool add_weight, int64_t edges_hint);
 torch::Tensor mlr_sparse_fwd(torch::Tensor row_ptr, torch::Tensor col,
                              torch::Tensor val, torch::Tensor Wt, int64_t C,
                              int64_t group);
@@ -222,6 +228,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pregel_pull", &pregel_pull,
         "Pregel send+combine as a CSR gather-reduce over the pull index "
         "(K13)");
+  m.def("pregel_push", &pregel_push,
+        "Pregel send+combine along the frontier's out-edges, min combiner "
+        "by integer atomics (K13p)");
   m.def("mlr_sparse_fwd", &mlr_sparse_fwd,
         "sparse MLR logits: CSR gather-reduce over W^T rows (K4s)");
   m.def("mlr_sparse_grad", &mlr_sparse_grad,

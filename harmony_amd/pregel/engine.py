@@ -100,9 +100,27 @@ class PullIndex:
     in_src: torch.Tensor           # int32 [Ein] local source vertex index
     in_w: Optional[torch.Tensor]   # float32 [Ein] or None
     remote_keys: torch.Tensor      # int64 [U] global ids of rows >= n_local
+    # destination row of every local edge in original edge order; kept only
+    # on request, for build_push_index, which takes it over
+    row_of_edge: Optional[torch.Tensor] = None   # int64 [E]
+
+    @property
+    def num_rows(self) -> int:
+        return int(self.in_ptr.shape[0]) - 1
 
 
-def build_pull_index(graph: LocalGraph, msg_table: Table) -> PullIndex:
+@dataclass
+class PushIndex:
+    """The local out-CSR with every destination renamed to its row in the
+    pull index's row space (see build_push_index)."""
+
+    out_ptr: torch.Tensor          # int64 [n_local+1]
+    out_row: torch.Tensor          # int32 [E] row in 0..R-1, edge order
+    out_w: Optional[torch.Tensor]  # float32 [E] or None
+
+
+def build_pull_index(graph: LocalGraph, msg_table: Table,
+                     keep_rows: bool = False) -> PullIndex:
     """Invert the local CSR into a pull index for ops.pregel_pull.
 
     Rows 0..n_local-1 are the local vertices in shard order (a vertex
@@ -114,7 +132,8 @@ def build_pull_index(graph: LocalGraph, msg_table: Table) -> PullIndex:
     The index is tied to `msg_table`'s ownership at the time of the call:
     which destinations are local rows and which are remote is baked in.
     Pregel tables do not migrate mid-run, so it is built once per job in
-    PregelEngine.set_graph."""
+    PregelEngine.set_graph. keep_rows leaves the per-edge destination rows
+    on the index for build_push_index."""
     dev = graph.edge_dst.device
     n_local = int(graph.row_ptr.shape[0]) - 1
     n_edges = int(graph.edge_dst.shape[0])
@@ -147,15 +166,99 @@ def build_pull_index(graph: LocalGraph, msg_table: Table) -> PullIndex:
         in_w = graph.edge_weight.to(torch.float32)[order].contiguous()
     return PullIndex(n_local=n_local, in_ptr=in_ptr,
                      in_src=src_local[order].to(torch.int32).contiguous(),
-                     in_w=in_w, remote_keys=remote_keys)
+                     in_w=in_w, remote_keys=remote_keys,
+                     row_of_edge=row_of_edge if keep_rows else None)
+
+
+def build_push_index(graph: LocalGraph, pull_index: PullIndex,
+                     msg_table: Table) -> PushIndex:
+    """The out-edge view of the same edge list for ops.pregel_push: the
+    graph's own CSR with out_row[e] = the pull index's row of edge e's
+    destination, so push and pull write the same [R] result and everything
+    after the op is shared.
+
+    The rows are the ones build_pull_index(keep_rows=True) computed while
+    numbering the remote destinations; they are taken over from
+    `pull_index` (and dropped there), not derived a second time, so the two
+    indexes cannot disagree. out_w is graph.edge_weight itself."""
+    rows = pull_index.row_of_edge
+    if rows is None:
+        raise ValueError("build_push_index needs a pull index built with "
+                         "keep_rows=True (its row_of_edge)")
+    if pull_index.num_rows >= 2 ** 31:
+        raise ValueError(
+            f"push index needs fewer than 2^31 rows, got "
+            f"{pull_index.num_rows}: out_row is int32")
+    pull_index.row_of_edge = None
+    out_w = graph.edge_weight
+    if out_w is not None and out_w.dtype != torch.float32:
+        out_w = out_w.to(torch.float32)
+    return PushIndex(out_ptr=graph.row_ptr.to(torch.int64).contiguous(),
+                     out_row=rows.to(torch.int32).contiguous(), out_w=out_w)
+
+
+# Default share of the local edges below which direction="auto" pushes.
+# Measured (scripts/pregel_push_ab.py, profiles/pregel_push_ab.md): on the
+# ring+random graph at 2^20 x 8 push, as the engine calls it, is no slower
+# than pull up to a share of 2^-4 of the edges, at 2^20 x 64 up to 2^-3;
+# the largest power of two that holds on both is 2^-4, halved once as a
+# margin because the crossover moves with degree and skew.
+DEFAULT_PUSH_THRESHOLD = 2.0 ** -5
+
+DIRECTIONS = ("pull", "push", "auto")
 
 
 class PregelEngine:
+    """BSP engine; see the module docstring.
+
+    fused=True sends and combines through ops.pregel_pull (K13) over the
+    pull index. `direction` chooses, for the fused path, which way a
+    superstep's messages travel:
+      "pull"  K13 over every in-edge of every row (the default);
+      "push"  K13p (ops.pregel_push) along the out-edges of the sending
+              vertices only; min combiner only;
+      "auto"  per rank and per superstep: push iff the out-degrees of the
+              sending vertices sum to less than push_threshold *
+              num_local_edges (strictly, so an empty frontier pushes, a
+              no-op), else pull. With the add combiner, or when everyone
+              sends (send_mask None), auto pulls.
+    Both ops give the same [R] result value for value, and everything after
+    them (local rows, remote rows, the vote, the one collective) is shared,
+    so ranks need not agree on the direction. push_supersteps and
+    pull_supersteps count the supersteps of the last run() that used each.
+
+    push_threshold defaults to DEFAULT_PUSH_THRESHOLD = 2^-5: the largest
+    power-of-two share at which push was measured no slower than pull on
+    both 2^20 x 8 and 2^20 x 64 (2^-4), halved once as a margin
+    (profiles/pregel_push_ab.md). "pull" and "push" add no host read to a
+    superstep; "auto" adds one, of the frontier's edge count. That read
+    costs more than the kernel saves where a superstep is bound by host
+    launches (low degree, high diameter), so "pull" stays the default."""
+
     def __init__(self, job: JobConfig, comp: Computation, num_vertices: int,
                  ctx, cp: ControlPlane, tus: Optional[TaskUnitScheduler] = None,
-                 max_supersteps: int = 100, fused: bool = False):
+                 max_supersteps: int = 100, fused: bool = False,
+                 direction: str = "pull",
+                 push_threshold: Optional[float] = None):
         self.job = job
         self.comp = comp
+        if direction not in DIRECTIONS:
+            raise ValueError(f"direction must be one of {DIRECTIONS}, "
+                             f"got {direction!r}")
+        if direction != "pull" and not fused:
+            raise ValueError(f"direction={direction!r} needs fused=True: "
+                             "the unfused path sends per-edge messages")
+        if direction == "push" and comp.combiner != "min":
+            raise ValueError(
+                "direction='push' supports the min combiner only, this "
+                f"computation combines with {comp.combiner!r}")
+        self.direction = direction
+        self.push_threshold = float(DEFAULT_PUSH_THRESHOLD
+                                    if push_threshold is None
+                                    else push_threshold)
+        self.push: Optional[PushIndex] = None
+        self.push_supersteps = 0
+        self.pull_supersteps = 0
         # fused: send + combine through the pull index (ops.pregel_pull,
         # K13) instead of per-edge messages + a combining scatter
         self.fused = bool(fused)
@@ -206,7 +309,17 @@ class PregelEngine:
         if self.fused:
             # both message tables share one layout; see build_pull_index
             # for why the index is valid for the whole run
-            self.pull = build_pull_index(graph, self.msg[0])
+            can_push = (self.direction != "pull"
+                        and self.comp.combiner == "min")
+            self.pull = build_pull_index(graph, self.msg[0],
+                                         keep_rows=can_push)
+            if can_push:
+                self.push = build_push_index(graph, self.pull, self.msg[0])
+                self._out_deg = (self.push.out_ptr[1:]
+                                 - self.push.out_ptr[:-1])
+                self._everyone = torch.arange(
+                    self.pull.n_local, dtype=torch.int32,
+                    device=self.push.out_ptr.device)
 
     def _next_phase(self):
         self._phase += 1
@@ -272,6 +385,22 @@ class PregelEngine:
         self.vertex_table.shard[:n_local] = values
         return values
 
+    def _push_or_pull(self, send_mask: Optional[torch.Tensor]):
+        """This superstep's direction: (True, the frontier's edge count or
+        -1) to push, (False, -1) to pull. "pull" and "push" cost no host
+        read (K13p takes the mask itself, over the frontier of all
+        vertices); "auto" costs one, of the frontier's edge count."""
+        if self.push is None:          # "pull", or "auto" with add
+            return False, -1
+        if self.direction == "push":
+            return True, -1
+        if send_mask is None:          # everyone sends
+            return False, -1
+        edges = int((self._out_deg * send_mask).sum())
+        if edges < self.push_threshold * self.push.out_row.shape[0]:
+            return True, edges
+        return False, -1
+
     def _run_fused(self) -> torch.Tensor:
         """run() with send + combine as ONE gather-reduce per superstep
         (K13): no per-edge message tensor, no per-superstep sort. Local
@@ -294,6 +423,7 @@ class PregelEngine:
         zero_msgs = torch.empty((0, 1), dtype=torch.float32, device=dev)
         add_weight = comp.edge_op == "add_weight"
         w_const = float(getattr(comp, "edge_weight", 0.0))
+        self.push_supersteps = self.pull_supersteps = 0
         for step in range(self.max_supersteps):
             self.supersteps_run = step + 1
             incoming = self.msg[self.cur].shard[:n_local]
@@ -308,10 +438,21 @@ class PregelEngine:
             if vert_msg is None:
                 vote = torch.stack([n_active, torch.zeros_like(n_active)])
             else:
-                out, flag = ops.pregel_pull(
-                    pull.in_ptr, pull.in_src, pull.in_w, w_const,
-                    vert_msg.to(torch.float32), send_mask, comp.combiner,
-                    add_weight)
+                pushing, hint = self._push_or_pull(send_mask)
+                if pushing:
+                    self.push_supersteps += 1
+                    out, flag = ops.pregel_push(
+                        self.push.out_ptr, self.push.out_row,
+                        self.push.out_w, w_const,
+                        vert_msg.to(torch.float32), self._everyone,
+                        pull.num_rows, comp.combiner, add_weight,
+                        send_mask=send_mask, _edges_hint=hint)
+                else:
+                    self.pull_supersteps += 1
+                    out, flag = ops.pregel_pull(
+                        pull.in_ptr, pull.in_src, pull.in_w, w_const,
+                        vert_msg.to(torch.float32), send_mask,
+                        comp.combiner, add_weight)
                 # local rows first: unflagged rows hold the identity, like
                 # the cleared shard, and the push below combines remote
                 # ranks' contributions on top of them

@@ -1,8 +1,9 @@
-"""Graph apps: PageRank + single-source shortest path.
+"""Graph apps: PageRank, single-source shortest path, connected components.
 
 Reference: pregel/graphapps/pagerank (PagerankComputation + sum combiner)
-and pregel/graphapps/shortestpath (min combiner). Both are vectorized over
-the local vertex partition (see engine.Computation).
+and pregel/graphapps/shortestpath (min combiner); connected components
+(min-label propagation) has no reference counterpart. All are vectorized
+over the local vertex partition (see engine.Computation).
 """
 
 from __future__ import annotations
@@ -123,6 +124,90 @@ class ShortestPathComputation(Computation):
         active = torch.zeros(values.shape[0], dtype=torch.bool,
                              device=values.device)
         return new, new.squeeze(1), changed, active
+
+
+CC_MAX_VERTICES = 2 ** 24
+
+
+class ConnectedComponentsComputation(Computation):
+    """Label propagation with a min combiner: every vertex starts with its
+    own global id as its label and sends it; afterwards a vertex adopts the
+    smallest incoming label and, when that improved its own, sends it on.
+    Vertices halt immediately; messages wake them. At the end label(v) is
+    the smallest id with a path to v, which on a symmetrised edge list is
+    the smallest id of v's weakly connected component.
+
+    Labels are float32 vertex ids, exact up to 2^24; a larger graph raises
+    ValueError here, before any table is built."""
+
+    combiner = "min"
+    msg_identity = float("inf")
+    msg_dim = 1
+    edge_op = "copy"
+
+    def __init__(self, num_vertices: int):
+        if num_vertices > CC_MAX_VERTICES:
+            raise ValueError(
+                f"connected components labels vertices with float32 ids, "
+                f"which are exact only up to 2^24 = {CC_MAX_VERTICES} "
+                f"vertices; got {num_vertices}")
+        self.num_vertices = num_vertices
+
+    def _relax(self, superstep, values, incoming, has_msg, graph):
+        """-> (new labels, mask of the vertices that improved)."""
+        n_local = values.shape[0]
+        if superstep == 0:
+            ids = torch.arange(graph.vertex_lo, graph.vertex_lo + n_local,
+                               device=values.device)
+            new = ids.to(values.dtype).unsqueeze(1)
+            changed = torch.ones(n_local, dtype=torch.bool,
+                                 device=values.device)
+        else:
+            cand = torch.where(has_msg.unsqueeze(1), incoming,
+                               torch.full_like(incoming, float("inf")))
+            new = torch.minimum(values, cand)
+            changed = (new < values).any(dim=1)
+        return new, changed
+
+    def compute(self, superstep, values, incoming, has_msg, graph: LocalGraph):
+        new, changed = self._relax(superstep, values, incoming, has_msg,
+                                   graph)
+        edge_msgs = None
+        if bool(changed.any()):
+            counts = graph.row_ptr[1:] - graph.row_ptr[:-1]
+            label_per_edge = new.squeeze(1).repeat_interleave(counts)
+            msgs = torch.where(changed.repeat_interleave(counts),
+                               label_per_edge,
+                               torch.full_like(label_per_edge, float("inf")))
+            edge_msgs = msgs.unsqueeze(1)
+        active = torch.zeros(values.shape[0], dtype=torch.bool,
+                             device=values.device)
+        return new, edge_msgs, active
+
+    def vertex_messages(self, superstep, values, incoming, has_msg,
+                        graph: LocalGraph):
+        """compute() with one message per vertex: an improved vertex sends
+        its label along all its out-edges as is."""
+        new, changed = self._relax(superstep, values, incoming, has_msg,
+                                   graph)
+        active = torch.zeros(values.shape[0], dtype=torch.bool,
+                             device=values.device)
+        return new, new.squeeze(1), changed, active
+
+
+def ring_plus_random_edges(num_vertices: int, out_degree: int, seed: int):
+    """The whole edge list of make_ring_plus_random_graph on the CPU:
+    (src int64 [n * deg], dst int64 [n * deg]), sources ascending."""
+    g = make_ring_plus_random_graph(num_vertices, out_degree, 0, num_vertices,
+                                    torch.device("cpu"), seed)
+    src = torch.arange(num_vertices, dtype=torch.int64).repeat_interleave(
+        out_degree)
+    return src, g.edge_dst.to(torch.int64)
+
+
+def symmetrise(src: torch.Tensor, dst: torch.Tensor):
+    """Append every edge reversed: (src ++ dst, dst ++ src)."""
+    return torch.cat([src, dst]), torch.cat([dst, src])
 
 
 def make_ring_plus_random_graph(num_vertices: int, out_degree: int,
