@@ -18,7 +18,19 @@ MI355X redesign (documented divergences):
     single-thread CPU optimization).
 
 App args: num_docs (global), num_vocabs, num_topics, tokens_per_doc, alpha,
-beta, docs_per_batch.
+beta, docs_per_batch; test_data_path, test_foldin_iters.
+
+test_data_path: a held-out file in the -input format (TestDataProvider).
+LDA has nothing to predict per row, so the metric is document completion
+(mlapps/heldout.py lda_test_set): of every held-out document the tokens at
+even positions are folded in against the frozen table for test_foldin_iters
+EM steps (kernel K7e, ops.lda_foldin), and the tokens at odd positions are
+scored under the resulting topic mixture. evaluate_test() reports
+test_log_likelihood, test_tokens, test_examples and test_perplexity =
+exp(-test_log_likelihood / test_tokens), for the final model and for every
+checkpoint under offline model evaluation. Unlike the training
+log-likelihood it does not reward over-fitting and it compares runs with
+different num_topics. Every rank reads and evaluates the whole file.
 """
 
 from __future__ import annotations
@@ -41,9 +53,10 @@ def defaults(job: JobConfig) -> dict:
              sampler="exact",   # "exact" (dense Gibbs) | "alias" (MH, K7b)
                                 # | "alias_wave" (K7c wave-per-doc MH)
              alias_refresh=4,   # rebuild alias tables every N pulls
-             packed=True)       # alias_wave: packed per-segment tables (K7d)
+             packed=True,       # alias_wave: packed per-segment tables (K7d)
                                 # when K/64 is 1, 2, 4 or 8; False keeps the
                                 # legacy arrays and kernels
+             test_foldin_iters=20)  # EM steps per held-out document (K7e)
     a.update(job.app_args)
     return a
 
@@ -151,6 +164,7 @@ class LDATrainer(Trainer):
         self._assignments = {}          # block index -> [n_tokens] int32
         self._epoch_seed = stable_seed(ctx.job_id, "gibbs", ctx.rank)
         self._step = 0
+        self.test_set = None            # heldout.LDATestSet, set by build()
 
     def initialize(self) -> None:
         """Random initial topic assignments; push the implied word-topic
@@ -424,12 +438,39 @@ class LDATrainer(Trainer):
                 "log_pw_given_z": float(lpw),
                 "log_pz_local": float(lpz)}
 
+    def evaluate_test(self):
+        """Held-out per-word perplexity by document completion (module
+        docstring; {} without test_data_path). Pulls the model as
+        evaluate_model does, a collective, so every rank calls it; reads
+        nothing of the training state."""
+        import math
+
+        ts = self.test_set
+        if ts is None:
+            return {}
+        a = self.a
+        V = a["num_vocabs"]
+        full = self.accessor.table.pull_all()[:V + 1]     # int32, as pulled
+        _theta, ll = ops.lda_foldin(
+            full[:V], full[V], ts.obs_ptr, ts.obs_word, ts.obs_cnt,
+            ts.sc_ptr, ts.sc_word, ts.sc_cnt, float(a["alpha"]),
+            float(a["beta"]), V, int(a["test_foldin_iters"]))
+        total = float(ll.double().sum())
+        return {"test_log_likelihood": total,
+                "test_tokens": ts.num_scored_tokens,
+                "test_examples": ts.num_docs,
+                "test_perplexity": math.exp(-total / ts.num_scored_tokens)}
+
     def num_batch_examples(self) -> int:
         return self.batch.num_examples
 
 
 
 def build(job: JobConfig, ctx, cp):
+    from harmony_amd.mlapps import heldout
+
+    # first, so that a missing or bad file fails before the table exists
+    test_set = heldout.lda_test_set(defaults(job), ctx.device)
     cfg = model_table_cfg(job, ctx.world_size)
     table = build_ps_table(job, cfg, ctx, cp)
     blocks, local_docs = make_batches(job, ctx.rank, ctx.device,
@@ -438,5 +479,6 @@ def build(job: JobConfig, ctx, cp):
                           world_size=ctx.world_size, device=ctx.device,
                           tables={MODEL_TABLE: table}, app_args=job.app_args)
     trainer = LDATrainer(tctx, local_docs, blocks)
+    trainer.test_set = test_set
     provider = TrainingDataProvider(blocks)
     return {MODEL_TABLE: table}, trainer, provider

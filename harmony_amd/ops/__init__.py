@@ -14,6 +14,7 @@ Kernel inventory (reference hot loops):
   K4  mlr softmax+grad    MLRTrainer.java:374-398,475-489
   K4s mlr_sparse_fwd/grad MLRTrainer.java:374-398 over SparseVector rows
   K7  lda_gibbs           SparseLDASampler.java:141-274
+  K7e lda_foldin          held-out document completion (TestDataProvider)
   K9  scatter-apply       LDAETModelUpdateFunction.java:43-64
   K10 gbt_hist            GBTTrainer.java:244+ (histogram method)
   K10b gbt_best_split     GBTTrainer.java bestSplitRealFeature/LabelFeature
@@ -749,6 +750,113 @@ def lda_apply_all(shard, word_rows, old_t, new_t, summary_row: int) -> None:
     srow = summary_row * K
     flat.scatter_add_(0, srow + o, -ones)
     flat.scatter_add_(0, srow + nw, ones)
+
+
+# ---------------------------------------------------------------------------
+# K7e: held-out fold-in (document completion) against the frozen table
+# ---------------------------------------------------------------------------
+
+LDA_FOLDIN_MAX_TOPICS = 1024        # ops/csrc/lda_foldin.hip: 64 lanes x 16
+_FOLDIN_CHUNK_ELEMS = 1 << 22       # torch path: floats per [pairs, K] chunk
+
+
+def _foldin_check(ptr: torch.Tensor, word: torch.Tensor, cnt: torch.Tensor,
+                  num_vocabs: int) -> torch.Tensor:
+    ok = (ptr[0] == 0) & (ptr[-1] == word.shape[0]) \
+        & (ptr[1:] >= ptr[:-1]).all()
+    if word.shape[0]:
+        ok = ok & (word.min() >= 0) & (word.max() < num_vocabs)
+    if cnt.shape[0] != word.shape[0]:
+        raise ValueError("lda_foldin: one count per (word, count) pair")
+    return ok
+
+
+def lda_foldin(word_topic: torch.Tensor, topic_sum: torch.Tensor,
+               obs_ptr: torch.Tensor, obs_word: torch.Tensor,
+               obs_cnt: torch.Tensor, sc_ptr: torch.Tensor,
+               sc_word: torch.Tensor, sc_cnt: torch.Tensor,
+               alpha: float, beta: float, num_vocabs: int, iters: int
+               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fold held-out documents in against the frozen model and score them
+    (K7e, ops/csrc/lda_foldin.hip): (theta float32 [D, K], ll float32 [D]).
+
+    word_topic: int32 [>= num_vocabs, K], contiguous (the [:V] view of the
+    pulled table qualifies), topic_sum: int32 [K]; both are read as they
+    are, no float copy of the table is made. Document d owns the (word,
+    count) pairs obs_ptr[d]:obs_ptr[d+1] of obs_word (int64) / obs_cnt
+    (int32), its observed half, and the pairs sc_ptr[d]:sc_ptr[d+1] of
+    sc_word / sc_cnt, its scored half; the ptr tensors are int64 [D + 1].
+
+      phi[w,k] = (n_wk + beta) / (n_k + V beta),         theta^0_k = 1/K
+      iters times:  m_k = sum_obs c theta_k phi[w,k] / sum_j theta_j phi[w,j]
+                    theta_k = (m_k + alpha) / (N_obs + K alpha)
+      ll = sum_scored c log sum_k theta_k phi[w,k]
+
+    All of it in float32, pairs in their stored order. The kernel couples no
+    two documents, so its result for a document is bitwise the same wherever
+    the document stands in the batch. CPU tensors, HARMONY_FORCE_TORCH_OPS=1
+    and K > LDA_FOLDIN_MAX_TOPICS take the tensor ops below, in chunks of
+    pairs, so that no [all_pairs, K] tensor is built; on a GPU their
+    index_add_ sums in no fixed order. D = 0 returns empty tensors without a
+    launch. A word id outside [0, num_vocabs) raises ValueError."""
+    K = int(word_topic.shape[1])
+    D = int(obs_ptr.shape[0]) - 1
+    dev = word_topic.device
+    if D < 0 or sc_ptr.shape[0] != D + 1:
+        raise ValueError("lda_foldin: obs_ptr and sc_ptr must be [D + 1]")
+    if word_topic.shape[0] < num_vocabs or topic_sum.shape[0] != K:
+        raise ValueError("lda_foldin: word_topic [>= num_vocabs, K] and "
+                         "topic_sum [K] expected")
+    if iters < 0:
+        raise ValueError("lda_foldin: iters must be >= 0")
+    if D == 0:
+        return (torch.empty(0, K, dtype=torch.float32, device=dev),
+                torch.empty(0, dtype=torch.float32, device=dev))
+    if not bool(_foldin_check(obs_ptr, obs_word, obs_cnt, num_vocabs)
+                & _foldin_check(sc_ptr, sc_word, sc_cnt, num_vocabs)):
+        raise ValueError("lda_foldin: a word id outside [0, num_vocabs) or "
+                         "pair offsets that do not match the pair arrays")
+    if _use_hip(word_topic) and K <= LDA_FOLDIN_MAX_TOPICS:
+        theta, ll = _hip.lda_foldin(
+            word_topic, topic_sum.contiguous(), obs_ptr.contiguous(),
+            obs_word.contiguous(), obs_cnt.contiguous(), sc_ptr.contiguous(),
+            sc_word.contiguous(), sc_cnt.contiguous(), float(alpha),
+            float(beta), int(num_vocabs), int(iters))
+        return theta, ll
+
+    invden = 1.0 / (topic_sum.float() + num_vocabs * beta)          # [K]
+    docs = torch.arange(D, device=dev)
+    obs_doc = torch.repeat_interleave(docs, obs_ptr[1:] - obs_ptr[:-1])
+    sc_doc = torch.repeat_interleave(docs, sc_ptr[1:] - sc_ptr[:-1])
+    n_obs = torch.zeros(D, dtype=torch.int64, device=dev).index_add_(
+        0, obs_doc, obs_cnt.long())
+    den = (n_obs.float() + float(K) * alpha).unsqueeze(1)
+    step = max(1, _FOLDIN_CHUNK_ELEMS // K)
+
+    def terms(ti, word, doc, lo):
+        """theta_k phi[w,k] of the pairs lo:lo+step and their totals."""
+        val = ti[doc[lo:lo + step]] * \
+            (word_topic[word[lo:lo + step]].float() + beta)
+        return val, val.sum(dim=1)
+
+    one = torch.ones((), dtype=torch.float32, device=dev)
+    theta = (one / torch.tensor(float(K), dtype=torch.float32, device=dev)
+             ).expand(D, K).contiguous()
+    for _ in range(int(iters)):
+        ti = theta * invden
+        m = torch.zeros(D, K, dtype=torch.float32, device=dev)
+        for lo in range(0, obs_word.shape[0], step):
+            val, tot = terms(ti, obs_word, obs_doc, lo)
+            scale = obs_cnt[lo:lo + step].float() / tot
+            m.index_add_(0, obs_doc[lo:lo + step], val * scale.unsqueeze(1))
+        theta = (m + alpha) / den
+    ti = theta * invden
+    ll = torch.zeros(D, dtype=torch.float32, device=dev)
+    for lo in range(0, sc_word.shape[0], step):
+        _val, tot = terms(ti, sc_word, sc_doc, lo)
+        ll.index_add_(0, sc_doc[lo:lo + step],
+                      sc_cnt[lo:lo + step].float() * torch.log(tot))
+    return theta, ll
 
 
 # K7d: packed per-segment tables for the wave sampler. rec[rows][64][4*S]

@@ -75,6 +75,12 @@ torch::Tensor lda_mh_wave_packed(torch::Tensor doc_topic,
                                  c10::optional<torch::Tensor> shard,
                                  c10::optional<torch::Tensor> row_of_local,
                                  int64_t summary_row);
+std::vector<torch::Tensor> lda_foldin(
+    torch::Tensor word_topic, torch::Tensor topic_sum, torch::Tensor obs_ptr,
+    torch::Tensor obs_word, torch::Tensor obs_cnt, torch::Tensor sc_ptr,
+    torch::Tensor sc_word, torch::Tensor sc_cnt, double alpha, double beta,
+    int64_t num_vocabs, int64_t iters);
+int64_t lda_foldin_max_topics();
 void lasso_cd(torch::Tensor Xt, torch::Tensor r, torch::Tensor w,
               torch::Tensor col_sq, double lam_n);
 int64_t lasso_cd_sparse_max_rows();
@@ -182,6 +188,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "alias tables as packed per-segment records (K7d)");
   m.def("lda_mh_wave_packed", &lda_mh_wave_packed,
         "wave-per-doc MH sweep over packed tables, optional fused apply (K7d)");
+  m.def("lda_foldin", &lda_foldin,
+        "held-out fold-in of documents against the frozen table (K7e)");
+  m.def("lda_foldin_max_topics", &lda_foldin_max_topics,
+        "largest num_topics K7e takes");
   m.def("gbt_hist", &gbt_hist, "GBT level histogram build (K10)");
   m.def("gbt_best_split", &gbt_best_split,
         "GBT per-node best split, continuous and categorical (K10b)");
