@@ -582,19 +582,28 @@ def _vose_serial(pr, al, lk, n):
         al[sm] = sm
 
 
+def lda_alias_build_batch() -> int:
+    """Rows a wave of the device build takes per batch (one lane per row for
+    the top-level Vose); tests size their row counts around it."""
+    assert _load_hip() is not None, _hip_err
+    return int(_hip.lda_alias_build_batch())
+
+
 def lda_alias_build(word_topic: torch.Tensor, topic_sum: torch.Tensor,
-                    beta: float, num_vocabs: int):
+                    beta: float, num_vocabs: int, max_workgroups=None):
     """Two-level per-word alias tables over the (batch-stale) word factor
     q_w(k) = (n_wk + b)/(n_k + V b): a 64-entry top alias over lane-segment
     masses + per-segment aliases (exact — see ops/csrc/lda_alias.hip).
     Returns (prob, alias, top_prob, top_alias, qsum, invden). Construction
     is deterministic and float-order-matched to the device kernel
     (butterfly total, ascending serial segment sums) so CPU and GPU build
-    bit-identical tables."""
+    bit-identical tables. max_workgroups caps the device launch (the rows
+    are then taken grid-strided); the CPU path ignores it."""
     if _use_hip(word_topic):
         return tuple(_hip.lda_alias_build(word_topic.contiguous(),
                                           topic_sum.contiguous(),
-                                          float(beta), int(num_vocabs)))
+                                          float(beta), int(num_vocabs),
+                                          max_workgroups))
     rows, K = word_topic.shape
     W = 64
     assert K % W == 0, "alias sampler requires K % 64 == 0"
@@ -889,20 +898,23 @@ def _rows32(src_rows):
 
 def lda_alias_build_packed(src: torch.Tensor, src_rows, topic_sum,
                            beta: float, num_vocabs: int, rec: torch.Tensor,
-                           top: torch.Tensor):
+                           top: torch.Tensor, max_workgroups=None):
     """lda_alias_build over rows `src[src_rows]` (or `src[:rows]` when
     src_rows is None; the former reads a table shard in place), written
     into the packed tables. Stored values are bit-identical to
-    lda_alias_build's. Returns (invden, qsum)."""
+    lda_alias_build's; the reserved slot of every record is set to zero,
+    which is what lda_packed_alloc left there. Returns (invden, qsum).
+    max_workgroups as for lda_alias_build."""
     if _use_hip(src):
         return tuple(_hip.lda_alias_build_packed(
             src, _rows32(src_rows), topic_sum.contiguous(), float(beta),
-            int(num_vocabs), rec, top))
+            int(num_vocabs), rec, top, max_workgroups))
     rows, S = rec.shape[0], rec.shape[2] // 4
     wt = src[src_rows.long()] if src_rows is not None else src[:rows]
     prob, alias, tprob, talias, qv, qsum, invden = lda_alias_build(
         wt, topic_sum, beta, num_vocabs)
     r = rec.view(rows, 64, 4, S)
+    r[:, :, 0] = 0      # reserved: rewritten so that records go out whole
     r[:, :, 1] = prob.view(torch.int32).view(rows, 64, S)
     r[:, :, 2] = qv.view(torch.int32).view(rows, 64, S)
     r[:, :, 3] = alias.view(rows, 64, S)

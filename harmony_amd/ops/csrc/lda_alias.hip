@@ -29,9 +29,13 @@
 //       row, plain ops; AtomicCounts: row shared by a wave). RNG: counter
 //       hash (hip_common.h) at ctr = token*8 + draw, mirrored by the torch
 //       reference for sample-exact CPU/GPU tests.
-//   alias_build_row<CS>            one row's tables in LDS (CS = compile-time
-//       S, or 0 for any K % 64 == 0). alias_build_kernel writes six arrays,
-//       alias_build_packed_kernel<S> packed records — the same bits.
+//   alias_build_row<CS>            the lane-parallel part of one row's build
+//       (CS = compile-time S, or 0 for any K % 64 == 0) and
+//   alias_build_batches<CS, Out>   the build of all rows, a batch of rows per
+//       wave with their top-level Vose chains side by side, one lane each.
+//       alias_build_kernel writes six arrays (LegacyOut),
+//       alias_build_packed_kernel<S> packed records (PackedOut<S>) — the
+//       same bits.
 //   lda_mh_kernel<PF>              K7b, thread per doc, u8 rows, exact vs the
 //       CPU oracle; PF prefetches the next token's top entry.
 //   lda_mh_wave_kernel<Tables, FUSED>  K7c/K7d, wave per doc, lanes take
@@ -49,7 +53,7 @@ constexpr int ALIAS_THREADS = 64;   // same-box interleaved A/B: 64 beats 128
                                     // (isolated 0.59 vs 0.655 ms; 3-job bench
                                     // 1.59/1.62 vs 1.63/1.66 ms/step) — the
                                     // earlier '64 = 1.74 ms' was cross-box noise
-constexpr int BUILD_WAVES = 4;
+constexpr int BUILD_WAVES = 4;       // waves per workgroup of the table build
 
 // ---------------------------------------------------------------- layout --
 // K7d packed tables. The legacy layout keeps [rows][K] / [rows][64] arrays
@@ -174,42 +178,87 @@ __device__ void vose_serial(float* pr, int* al, int* lk, int n) {
                            pr[sm] = 1.f; al[sm] = sm; }
 }
 
-// One wave's LDS scratch for a row:
-// pr[K] f32 | al[K] i32 | lk[K] i32 | tp[64] f32 | ta[64] i32 | tl[64] i32
+// The top-level Vose is one lane's chain of dependent LDS round trips (a
+// 64-step classification, then up to ~64 pops of 2-3 round trips each):
+// one row per wave leaves 63 lanes idle for its whole length and a CU with
+// at most 32 chains in flight. A wave therefore builds a BATCH of rows: the
+// lane-parallel part row after row (phase 1), then lane r runs the top
+// Vose of row r of the batch (phase 2), then all lanes write the top tables
+// (phase 3). Measured at 100 000 rows, K = 256 (profiles/
+// lda_build_batched.md): B = 4 with 4 waves per workgroup is the fastest of
+// B = 2..64; a larger batch costs more in resident waves for phase 1 than
+// its longer phase 2 gives back. 8-bit top indices and a prefetch of the
+// next row's counts were measured too and did not pay.
+constexpr int BUILD_BATCH = 4;     // rows per wave and batch, <= 64
+// row stride of the batch's top arrays: an odd number of words, so lanes
+// reading index k of their own rows hit different banks
+constexpr int TOP_STRIDE = WAVE + 1;
+static_assert(BUILD_BATCH >= 1 && BUILD_BATCH <= WAVE, "one lane per row");
+
+// One wave's LDS scratch:
+//   pr[K] f32 | al[K] i32 | lk[K] i32       entry tables of the current row
+//   tp[B][TOP_STRIDE] f32 | ta[B][TOP_STRIDE] i32 | tl[B][TOP_STRIDE] i32
+//                                           top tables of the batch's B rows
 struct BuildLds {
   float* pr; int* al; int* lk; float* tp; int* ta; int* tl;
+  __host__ __device__ static constexpr size_t words(int K) {
+    return 3 * (size_t)K + 3 * (size_t)BUILD_BATCH * TOP_STRIDE;
+  }
   __device__ __forceinline__ BuildLds(float* smem, int wave, int K) {
-    pr = smem + (size_t)wave * (3 * (size_t)K + 3 * WAVE);
+    pr = smem + (size_t)wave * words(K);
     al = (int*)(pr + K);
     lk = al + K;
     tp = (float*)(lk + K);
-    ta = (int*)(tp + WAVE);
-    tl = ta + WAVE;
+    ta = (int*)(tp + BUILD_BATCH * TOP_STRIDE);
+    tl = ta + BUILD_BATCH * TOP_STRIDE;
   }
 };
 
-// One row of alias tables, built by one wave. Lane `lane` owns the segment
-// [lane*S, (lane+1)*S): it reads its S counts at cnt_p and writes the S
-// proposal densities qv = p/total (what the tables encode; the stale-table
-// acceptance needs it) at qv_p. On return the LDS holds the entry tables
-// (l.pr, l.al) and the top table (l.tp, l.ta), visible to every lane; the
-// row's total mass is returned on every lane. CS > 0 fixes S at compile
-// time (16-byte accesses, unrolled), CS == 0 takes any S_rt.
+// What one lane stored to LDS becomes readable by the other lanes of its
+// wave: without the fence pair the compiler forwards each lane's own
+// earlier store instead of reading what another lane wrote.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A lane's S counts of one row: CS > 0 loads them whole (16-byte accesses),
+// CS == 0 reads them in place for any run-time S.
+template <int CS> struct SegCounts {
+  int v[CS];
+  __device__ __forceinline__ void load(const int* __restrict__ p) {
+    ld_slot<CS>(p, v);
+  }
+  __device__ __forceinline__ int operator[](int i) const { return v[i]; }
+};
+template <> struct SegCounts<0> {
+  const int* p;
+  __device__ __forceinline__ void load(const int* __restrict__ p_) { p = p_; }
+  __device__ __forceinline__ int operator[](int i) const { return p[i]; }
+};
+
+// The lane-parallel part of one row's build (phase 1), by one wave. Lane
+// `lane` owns the segment [lane*S, (lane+1)*S): from its S counts it writes
+// the S proposal densities qv = p/total (what the tables encode; the
+// stale-table acceptance needs it) at qv_p, builds its segment's entry
+// table in LDS (l.pr, l.al at lane*S, read back by the same lane without a
+// fence) and stores the segment's top-table input, its mass normalized to
+// mean 1 across the 64, to tp_row[lane]. The row's total mass is returned
+// on every lane. CS > 0 fixes S at compile time (unrolled), CS == 0 takes
+// any S_rt.
 template <int CS>
 __device__ __forceinline__ float alias_build_row(
-    const BuildLds& l, int lane, int S_rt, const int* __restrict__ cnt_p,
-    const float* __restrict__ invden, float beta, int* __restrict__ qv_p) {
+    const BuildLds& l, float* tp_row, int lane, int S_rt,
+    const SegCounts<CS>& cnt, const float* __restrict__ invden, float beta,
+    int* __restrict__ qv_p) {
   constexpr int N = CS > 0 ? CS : 1;
   const int S = CS > 0 ? CS : S_rt;
   float* pr = l.pr + lane * S;
   const float* inv = invden + lane * S;
-  int v[N];
-  if constexpr (CS > 0) ld_slot<N>(cnt_p, v);
   float seg_mass = 0.f;
   for (int i = 0; i < S; ++i) {
-    int n;
-    if constexpr (CS > 0) n = v[i]; else n = cnt_p[i];
-    const float c = (float)n + beta;
+    const float c = (float)cnt[i] + beta;
     pr[i] = c * inv[i];
     // the stored p is rounded, the mass takes the product unrounded: a
     // fused multiply-add, written out so that the compiler's contraction
@@ -220,6 +269,7 @@ __device__ __forceinline__ float alias_build_row(
   const float total = wave_reduce_sum(seg_mass);
   const float inv_total = 1.f / total;
   if constexpr (CS > 0) {
+    int v[N];
     for (int i = 0; i < S; ++i) v[i] = __float_as_int(pr[i] * inv_total);
     st_slot<N>(qv_p, v);
   } else {
@@ -230,87 +280,160 @@ __device__ __forceinline__ float alias_build_row(
   const float sscale = (seg_mass > 0.f) ? (float)S / seg_mass : 0.f;
   for (int i = 0; i < S; ++i) pr[i] *= sscale;
   vose_serial(pr, l.al + lane * S, l.lk + lane * S, S);
-  // top alias over segment masses (normalized to mean 1 across 64)
-  l.tp[lane] = seg_mass * (float)WAVE / total;
-  if (lane == 0) vose_serial(l.tp, l.ta, l.tl, WAVE);
-  // lanes 1..63 read what lane 0 just wrote to tp/ta (and the dense
-  // write-back reads other lanes' segments): without the fence the
-  // compiler forwards each lane's own earlier store of tp[lane]
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  // top alias input: segment masses normalized to mean 1 across 64
+  tp_row[lane] = seg_mass * (float)WAVE / total;
   return total;
 }
 
 // Dense rows in, six arrays out; any K % 64 == 0.
-__global__ void alias_build_kernel(const int* __restrict__ word_topic,
-                                   const float* __restrict__ invden,
-                                   float beta,
-                                   float* __restrict__ prob,     // [rows][K]
-                                   int* __restrict__ alias,      // [rows][K]
-                                   float* __restrict__ top_prob, // [rows][64]
-                                   int* __restrict__ top_alias,  // [rows][64]
-                                   float* __restrict__ qv,       // [rows][K]
-                                   float* __restrict__ qsum,     // [rows]
-                                   int rows, int K) {
-  extern __shared__ float smem_f[];
-  const int wave = threadIdx.x / WAVE;
-  const int lane = threadIdx.x % WAVE;
-  const BuildLds l(smem_f, wave, K);
-  const int S = K / WAVE;                  // entries per lane segment
-  const int waves_wg = blockDim.x / WAVE;
-  for (int row = blockIdx.x * waves_wg + wave; row < rows;
-       row += gridDim.x * waves_wg) {
-    const int64_t base = (int64_t)row * K;
-    const float total = alias_build_row<0>(
-        l, lane, S, word_topic + base + lane * S, invden, beta,
-        reinterpret_cast<int*>(qv) + base + lane * S);
+struct LegacyOut {
+  const int* __restrict__ word_topic;
+  float* __restrict__ prob;      // [rows][K]
+  int* __restrict__ alias;       // [rows][K]
+  float* __restrict__ top_prob;  // [rows][64]
+  int* __restrict__ top_alias;   // [rows][64]
+  float* __restrict__ qv;        // [rows][K]
+  float* __restrict__ qsum;      // [rows]
+  int K;
+  __device__ __forceinline__ int src_row(int row) const { return row; }
+  __device__ __forceinline__ const int* counts(int srow, int lane,
+                                               int S) const {
+    return word_topic + (int64_t)srow * K + lane * S;
+  }
+  __device__ __forceinline__ int* qv_slot(int row, int lane, int S) const {
+    return reinterpret_cast<int*>(qv) + (int64_t)row * K + lane * S;
+  }
+  __device__ __forceinline__ void entries(const BuildLds& l, int row, int lane,
+                                          int S, float total) const {
     if (lane == 0) qsum[row] = total;
-    // coalesced write-back
+    // coalesced write-back: reads the other lanes' segments
+    wave_lds_sync();
+    const int64_t base = (int64_t)row * K;
     for (int c = 0; c < S; ++c) {
       const int k = c * WAVE + lane;
       prob[base + k] = l.pr[k];
       alias[base + k] = l.al[k];
     }
-    top_prob[(int64_t)row * WAVE + lane] = l.tp[lane];
-    top_alias[(int64_t)row * WAVE + lane] = l.ta[lane];
   }
-}
+  __device__ __forceinline__ void top(int row, int lane, float tp,
+                                      int ta) const {
+    top_prob[(int64_t)row * WAVE + lane] = tp;
+    top_alias[(int64_t)row * WAVE + lane] = ta;
+  }
+};
 
 // The row read through src_rows (the table shard in place) or densely, and
 // the tables written as packed records; S in {1, 2, 4, 8}.
-template <int S>
-__global__ void alias_build_packed_kernel(const int* __restrict__ src,
-                                          const int* __restrict__ src_rows,
-                                          const float* __restrict__ invden,
-                                          float beta,
-                                          int* __restrict__ rec,   // [rows][64][4S]
-                                          int2* __restrict__ top,  // [rows][64]
-                                          float* __restrict__ qsum,
-                                          int rows) {
-  constexpr int K = S * WAVE;
-  extern __shared__ float smem_f[];
+template <int S_>
+struct PackedOut {
+  const int* __restrict__ src;
+  const int* __restrict__ src_rows;
+  int* __restrict__ rec;      // [rows][64][4S]
+  int2* __restrict__ tops;    // [rows][64]
+  float* __restrict__ qsum;   // [rows]
+  __device__ __forceinline__ int src_row(int row) const {
+    return src_rows ? src_rows[row] : row;
+  }
+  __device__ __forceinline__ const int* counts(int srow, int lane, int) const {
+    return src + ((int64_t)srow * WAVE + lane) * S_;
+  }
+  __device__ __forceinline__ int* slot(int row, int lane) const {
+    return rec + ((int64_t)row * WAVE + lane) * (4 * S_);
+  }
+  __device__ __forceinline__ int* qv_slot(int row, int lane, int) const {
+    return slot(row, lane) + 2 * S_;
+  }
+  __device__ __forceinline__ void entries(const BuildLds& l, int row, int lane,
+                                          int, float total) const {
+    if (lane == 0) qsum[row] = total;
+    int* r = slot(row, lane);
+    int out[S_];
+    // the reserved slot holds zeros (lda_packed_alloc); storing them again
+    // makes the record a whole 16*S bytes written, so that no cache line
+    // goes to memory with a hole in it and has to be read first
+#pragma unroll
+    for (int i = 0; i < S_; ++i) out[i] = 0;
+    st_slot<S_>(r, out);                                 // reserved
+#pragma unroll
+    for (int i = 0; i < S_; ++i) out[i] = __float_as_int(l.pr[lane * S_ + i]);
+    st_slot<S_>(r + S_, out);                            // prob
+#pragma unroll
+    for (int i = 0; i < S_; ++i) out[i] = l.al[lane * S_ + i];
+    st_slot<S_>(r + 3 * S_, out);                        // alias
+  }
+  __device__ __forceinline__ void top(int row, int lane, float tp,
+                                      int ta) const {
+    tops[(int64_t)row * WAVE + lane] = make_int2(__float_as_int(tp), ta);
+  }
+};
+
+// All rows' tables, a batch of up to BUILD_BATCH consecutive rows per wave
+// and grid-stride step. Everything that does not depend on the top table
+// (qv, qsum, the entry tables) goes to `out` in phase 1.
+template <int CS, class Out>
+__device__ __forceinline__ void alias_build_batches(
+    float* smem, const Out& out, const float* __restrict__ invden, float beta,
+    int rows, int K) {
   const int wave = threadIdx.x / WAVE;
   const int lane = threadIdx.x % WAVE;
-  const BuildLds l(smem_f, wave, K);
+  const BuildLds l(smem, wave, K);
+  const int S = K / WAVE;                  // entries per lane segment
   const int waves_wg = blockDim.x / WAVE;
-  for (int row = blockIdx.x * waves_wg + wave; row < rows;
-       row += gridDim.x * waves_wg) {
-    const int64_t base = (int64_t)(src_rows ? src_rows[row] : row) * K;
-    int* r = rec + ((int64_t)row * WAVE + lane) * (4 * S);
-    const float total = alias_build_row<S>(l, lane, S, src + base + lane * S,
-                                           invden, beta, r + 2 * S);   // qv
-    if (lane == 0) qsum[row] = total;
-    int out[S];
-#pragma unroll
-    for (int i = 0; i < S; ++i) out[i] = __float_as_int(l.pr[lane * S + i]);
-    st_slot<S>(r + S, out);                             // prob
-#pragma unroll
-    for (int i = 0; i < S; ++i) out[i] = l.al[lane * S + i];
-    st_slot<S>(r + 3 * S, out);                         // alias
-    top[(int64_t)row * WAVE + lane] =
-        make_int2(__float_as_int(l.tp[lane]), l.ta[lane]);
+  const int64_t step = (int64_t)gridDim.x * waves_wg * BUILD_BATCH;
+  for (int64_t b0 = ((int64_t)blockIdx.x * waves_wg + wave) * BUILD_BATCH;
+       b0 < rows; b0 += step) {
+    // rows of this batch; past `rows` nothing is read or written
+    const int nb = (int)min((int64_t)BUILD_BATCH, (int64_t)rows - b0);
+    // phase 1, row by row, lane = segment
+    const int my_src = lane < nb ? out.src_row((int)b0 + lane) : 0;
+    for (int r = 0; r < nb; ++r) {
+      const int row = (int)b0 + r;
+      SegCounts<CS> cnt;
+      cnt.load(out.counts(__shfl(my_src, r), lane, S));
+      const float total = alias_build_row<CS>(
+          l, l.tp + r * TOP_STRIDE, lane, S, cnt, invden, beta,
+          out.qv_slot(row, lane, S));
+      out.entries(l, row, lane, S, total);
+    }
+    // phase 2, lane = row: the same Vose, rows side by side; lanes differ
+    // in trip count only
+    wave_lds_sync();
+    if (lane < nb)
+      vose_serial(l.tp + lane * TOP_STRIDE, l.ta + lane * TOP_STRIDE,
+                  l.tl + lane * TOP_STRIDE, WAVE);
+    wave_lds_sync();
+    // phase 3, lane = segment again
+    for (int r = 0; r < nb; ++r)
+      out.top((int)b0 + r, lane, l.tp[r * TOP_STRIDE + lane],
+              l.ta[r * TOP_STRIDE + lane]);
   }
+}
+
+// The build kernels are compiled without packed fp32 instructions: every
+// table entry has to come out bit for bit, plain scalar IEEE operations are
+// the form the torch reference mirrors, and a latency-bound kernel has no
+// use for the packed ones.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LDA_BUILD_SCALAR_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define LDA_BUILD_SCALAR_F32
+#endif
+
+__global__ LDA_BUILD_SCALAR_F32
+void alias_build_kernel(const LegacyOut out,
+                        const float* __restrict__ invden, float beta,
+                        int rows) {
+  extern __shared__ float smem_f[];
+  alias_build_batches<0>(smem_f, out, invden, beta, rows, out.K);
+}
+
+template <int S>
+__global__ LDA_BUILD_SCALAR_F32
+void alias_build_packed_kernel(const PackedOut<S> out,
+                               const float* __restrict__ invden,
+                               float beta, int rows) {
+  extern __shared__ float smem_f[];
+  alias_build_batches<S>(smem_f, out, invden, beta, rows, S * WAVE);
 }
 
 // ------------------------------------------------------------ token step --
@@ -609,13 +732,27 @@ torch::Tensor build_invden(const torch::Tensor& topic_sum, double beta,
   return invden.contiguous();
 }
 
-// One wave per row, grid-strided; LDS as laid out by BuildLds.
+// One wave per batch of BUILD_BATCH rows, grid-strided; LDS as laid out by
+// BuildLds, kept within the 64 KiB a workgroup gets without opting in (a
+// wide legacy K runs fewer waves per workgroup). max_wgs caps the grid so
+// that a test reaches the grid-stride loop with few rows.
 struct BuildLaunch {
   dim3 grid, blk;
   size_t shmem;
-  BuildLaunch(int rows, int K, int waves)
-      : grid(std::min((rows + waves - 1) / waves, 8192)), blk(WAVE * waves),
-        shmem((size_t)waves * (3 * K + 3 * WAVE) * 4) {}
+  BuildLaunch(int rows, int K, c10::optional<int64_t> max_wgs) {
+    int waves = BUILD_WAVES;
+    const size_t wave_bytes = BuildLds::words(K) * 4;
+    while (waves > 1 && waves * wave_bytes > 64 * 1024) waves /= 2;
+    TORCH_CHECK(wave_bytes <= 64 * 1024, "K too large for the alias build");
+    TORCH_CHECK(!max_wgs.has_value() || *max_wgs >= 1,
+                "max_workgroups must be positive");
+    const int64_t batches = ((int64_t)rows + BUILD_BATCH - 1) / BUILD_BATCH;
+    int64_t wgs = std::min<int64_t>((batches + waves - 1) / waves, 8192);
+    if (max_wgs.has_value()) wgs = std::min(wgs, *max_wgs);
+    grid = dim3((unsigned)wgs);
+    blk = dim3(WAVE * waves);
+    shmem = waves * wave_bytes;
+  }
 };
 
 // lda_mh and lda_mh_wave: the same arguments over the legacy arrays, thread
@@ -675,9 +812,11 @@ torch::Tensor launch_legacy_mh(bool wave, torch::Tensor doc_topic,
 
 }  // namespace
 
-std::vector<torch::Tensor> lda_alias_build(torch::Tensor word_topic,
-                                           torch::Tensor topic_sum,
-                                           double beta, int64_t num_vocabs) {
+int64_t lda_alias_build_batch() { return BUILD_BATCH; }
+
+std::vector<torch::Tensor> lda_alias_build(
+    torch::Tensor word_topic, torch::Tensor topic_sum, double beta,
+    int64_t num_vocabs, c10::optional<int64_t> max_workgroups) {
   CHECK_IN(word_topic); CHECK_IN(topic_sum);
   TORCH_CHECK(word_topic.dtype() == torch::kInt32);
   const int rows = word_topic.size(0), K = word_topic.size(1);
@@ -693,17 +832,14 @@ std::vector<torch::Tensor> lda_alias_build(torch::Tensor word_topic,
                          word_topic.options().dtype(torch::kFloat32));
   auto qsum = torch::empty({rows}, prob.options());
   if (rows > 0) {
-    int waves = BUILD_WAVES;       // HARMONY_LDA_BUILD_WAVES: occupancy A/B
-    const char* bw = getenv("HARMONY_LDA_BUILD_WAVES");
-    if (bw) { int w = atoi(bw); if (w >= 1 && w <= 8) waves = w; }
-    const BuildLaunch L(rows, K, waves);
+    const BuildLaunch L(rows, K, max_workgroups);
+    const LegacyOut out{word_topic.data_ptr<int>(), prob.data_ptr<float>(),
+                        alias.data_ptr<int>(), top_prob.data_ptr<float>(),
+                        top_alias.data_ptr<int>(), qv.data_ptr<float>(),
+                        qsum.data_ptr<float>(), K};
     hipLaunchKernelGGL(alias_build_kernel, L.grid, L.blk, L.shmem,
-                       current_stream(),
-                       word_topic.data_ptr<int>(), invden.data_ptr<float>(),
-                       (float)beta, prob.data_ptr<float>(),
-                       alias.data_ptr<int>(), top_prob.data_ptr<float>(),
-                       top_alias.data_ptr<int>(), qv.data_ptr<float>(),
-                       qsum.data_ptr<float>(), rows, K);
+                       current_stream(), out, invden.data_ptr<float>(),
+                       (float)beta, rows);
   }
   return {prob, alias, top_prob, top_alias, qv, qsum, invden};
 }
@@ -774,7 +910,8 @@ static const int* check_rows(const c10::optional<torch::Tensor>& src_rows,
 std::vector<torch::Tensor> lda_alias_build_packed(
     torch::Tensor src, c10::optional<torch::Tensor> src_rows,
     torch::Tensor topic_sum, double beta, int64_t num_vocabs,
-    torch::Tensor rec, torch::Tensor top) {
+    torch::Tensor rec, torch::Tensor top,
+    c10::optional<int64_t> max_workgroups) {
   CHECK_IN(topic_sum);
   const int S_ = packed_S(rec, top);
   const int rows = rec.size(0), K = S_ * WAVE;
@@ -783,13 +920,14 @@ std::vector<torch::Tensor> lda_alias_build_packed(
   auto invden = build_invden(topic_sum, beta, num_vocabs);
   auto qsum = torch::empty({rows}, invden.options());
   if (rows > 0) {
-    const BuildLaunch L(rows, K, BUILD_WAVES);
+    const BuildLaunch L(rows, K, max_workgroups);
     LDA_DISPATCH_S(S_, hipLaunchKernelGGL(
         alias_build_packed_kernel<S>, L.grid, L.blk, L.shmem,
         current_stream(),
-        src.data_ptr<int>(), rows_p, invden.data_ptr<float>(), (float)beta,
-        rec.data_ptr<int>(), reinterpret_cast<int2*>(top.data_ptr<int>()),
-        qsum.data_ptr<float>(), rows));
+        PackedOut<S>{src.data_ptr<int>(), rows_p, rec.data_ptr<int>(),
+                     reinterpret_cast<int2*>(top.data_ptr<int>()),
+                     qsum.data_ptr<float>()},
+        invden.data_ptr<float>(), (float)beta, rows));
   }
   return {invden, qsum};
 }

@@ -44,9 +44,10 @@ void lda_apply_pairs(torch::Tensor shard, torch::Tensor rows,
 void lda_apply_all(torch::Tensor shard, torch::Tensor word_rows,
                    torch::Tensor old_t, torch::Tensor new_t,
                    int64_t summary_row);
-std::vector<torch::Tensor> lda_alias_build(torch::Tensor word_topic,
-                                           torch::Tensor topic_sum,
-                                           double beta, int64_t num_vocabs);
+std::vector<torch::Tensor> lda_alias_build(
+    torch::Tensor word_topic, torch::Tensor topic_sum, double beta,
+    int64_t num_vocabs, c10::optional<int64_t> max_workgroups);
+int64_t lda_alias_build_batch();
 torch::Tensor lda_mh_wave(torch::Tensor doc_topic, torch::Tensor word_topic,
                           torch::Tensor invden, torch::Tensor prob,
                           torch::Tensor alias, torch::Tensor top_prob,
@@ -64,7 +65,8 @@ torch::Tensor lda_mh(torch::Tensor doc_topic, torch::Tensor word_topic,
 std::vector<torch::Tensor> lda_alias_build_packed(
     torch::Tensor src, c10::optional<torch::Tensor> src_rows,
     torch::Tensor topic_sum, double beta, int64_t num_vocabs,
-    torch::Tensor rec, torch::Tensor top);
+    torch::Tensor rec, torch::Tensor top,
+    c10::optional<int64_t> max_workgroups);
 torch::Tensor lda_mh_wave_packed(torch::Tensor doc_topic,
                                  torch::Tensor word_topic, torch::Tensor rec,
                                  torch::Tensor top, torch::Tensor invden,
@@ -179,13 +181,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lda_apply_all", &lda_apply_all,
         "fused local token-delta + summary update (K9, single-owner path)");
   m.def("lda_alias_build", &lda_alias_build,
-        "per-word Vose alias tables over the stale word factor (K7b)");
+        "per-word Vose alias tables over the stale word factor (K7b)",
+        py::arg("word_topic"), py::arg("topic_sum"), py::arg("beta"),
+        py::arg("num_vocabs"), py::arg("max_workgroups") = py::none());
+  m.def("lda_alias_build_batch", &lda_alias_build_batch,
+        "rows a wave of the alias build takes per batch");
   m.def("lda_mh", &lda_mh,
         "Metropolis-Hastings alias LDA sweep, thread-per-doc (K7b)");
   m.def("lda_mh_wave", &lda_mh_wave,
         "wave-per-doc MH sweep (K7c, approximate within-doc parallelism)");
   m.def("lda_alias_build_packed", &lda_alias_build_packed,
-        "alias tables as packed per-segment records (K7d)");
+        "alias tables as packed per-segment records (K7d)",
+        py::arg("src"), py::arg("src_rows"), py::arg("topic_sum"),
+        py::arg("beta"), py::arg("num_vocabs"), py::arg("rec"),
+        py::arg("top"), py::arg("max_workgroups") = py::none());
   m.def("lda_mh_wave_packed", &lda_mh_wave_packed,
         "wave-per-doc MH sweep over packed tables, optional fused apply (K7d)");
   m.def("lda_foldin", &lda_foldin,
