@@ -66,12 +66,20 @@ __global__ void gbt_hist_kernel(
 
 void gbt_hist(torch::Tensor bins, torch::Tensor resid, torch::Tensor node,
               torch::Tensor cnt, torch::Tensor sum) {
+  check_tensor(__func__, bins, "bins", torch::kInt32, {-1, -1});
   const int B = bins.size(0), F = bins.size(1);
+  check_tensor(__func__, resid, "resid", torch::kFloat32, {B});
+  check_tensor(__func__, node, "node", torch::kInt32, {B});
+  check_tensor(__func__, cnt, "cnt", torch::kFloat32, {-1, F, -1});
   const int n_nodes = cnt.size(0), nb = cnt.size(2);
-  TORCH_CHECK(bins.scalar_type() == torch::kInt32 &&
-              node.scalar_type() == torch::kInt32, "bins/node must be int32");
-  TORCH_CHECK((long)n_nodes * nb <= LDS_ENTRIES,
-              "level too wide for LDS histogram (use torch fallback)");
+  check_tensor(__func__, sum, "sum", torch::kFloat32, {n_nodes, F, nb});
+  check_below_2_31(__func__, {{"B", bins.size(0)}, {"F", bins.size(1)}});
+  TORCH_CHECK(n_nodes >= 1 && nb >= 1, __func__,
+              ": cnt needs n_nodes, nb >= 1");
+  TORCH_CHECK((long)n_nodes * nb <= LDS_ENTRIES, __func__,
+              ": level too wide for LDS histogram (use torch fallback)");
+  check_on_device(__func__, {bins, resid, node, cnt, sum});
+  if (B == 0 || F == 0) return;
   const int fc = std::min((long)F, (long)(LDS_ENTRIES / (n_nodes * nb)));
   const int n_chunks = (F + fc - 1) / fc;
   // enough sample tiles to fill the chip once chunks are counted in

@@ -152,8 +152,6 @@ __global__ __launch_bounds__(HS_THREADS) void gbt_hist_sparse_kernel(
   }
 }
 
-constexpr int64_t kI31 = (int64_t)1 << 31;
-
 }  // namespace
 
 // The widest level (n_nodes * nb) K10s keeps in LDS.
@@ -166,56 +164,45 @@ std::vector<torch::Tensor> gbt_hist_sparse(
     torch::Tensor feat_idx, torch::Tensor zero_bin, torch::Tensor resid,
     torch::Tensor node, torch::Tensor node_cnt, torch::Tensor node_sum,
     int64_t nb) {
-  CHECK_IN(feat_ptr); CHECK_IN(feat_row); CHECK_IN(feat_bin);
-  CHECK_IN(feat_idx); CHECK_IN(zero_bin); CHECK_IN(resid); CHECK_IN(node);
-  CHECK_IN(node_cnt); CHECK_IN(node_sum);
-  TORCH_CHECK(feat_ptr.dtype() == torch::kInt64 && feat_ptr.dim() == 1 &&
-              feat_ptr.numel() >= 1, "feat_ptr must be int64 [nf+1]");
+  check_tensor(__func__, feat_ptr, "feat_ptr", torch::kInt64, {-1});
+  check_tensor(__func__, feat_row, "feat_row", torch::kInt32, {-1});
   const int64_t nf = feat_ptr.numel() - 1, nnz = feat_row.numel();
-  const int64_t B = resid.numel(), n_nodes = node_cnt.numel();
-  TORCH_CHECK(feat_row.dtype() == torch::kInt32 && feat_row.dim() == 1 &&
-              feat_bin.dtype() == torch::kInt32 && feat_bin.dim() == 1 &&
-              feat_idx.dtype() == torch::kInt32 && feat_idx.dim() == 1 &&
-              feat_bin.numel() == nnz && feat_idx.numel() == nnz,
-              "feat_row, feat_bin, feat_idx must be int32 [nnz]");
-  TORCH_CHECK(zero_bin.dtype() == torch::kInt32 && zero_bin.dim() == 1 &&
-              zero_bin.numel() == nf, "zero_bin must be int32 [nf]");
-  TORCH_CHECK(resid.dtype() == torch::kFloat32 && resid.dim() == 1,
-              "resid must be float32 [B]");
-  TORCH_CHECK(node.dtype() == torch::kInt32 && node.dim() == 1 &&
-              node.numel() == B, "node must be int32 [B]");
-  TORCH_CHECK(node_cnt.dtype() == torch::kFloat32 && node_cnt.dim() == 1 &&
-              node_sum.dtype() == torch::kFloat32 && node_sum.dim() == 1 &&
-              node_sum.numel() == n_nodes,
-              "node_cnt and node_sum must be float32 [n_nodes]");
-  TORCH_CHECK(nb >= 1 && n_nodes >= 1, "gbt_hist_sparse: nb, n_nodes >= 1");
-  TORCH_CHECK(n_nodes * nb <= HS_LDS_ENTRIES,
-              "level too wide for LDS histogram (use the torch path)");
-  TORCH_CHECK(B < kI31 && nf < kI31 && nnz < kI31 * 4,
-              "gbt_hist_sparse: B and nf must be below 2^31, nnz below 2^33");
+  check_tensor(__func__, feat_bin, "feat_bin", torch::kInt32, {nnz});
+  check_tensor(__func__, feat_idx, "feat_idx", torch::kInt32, {nnz});
+  check_tensor(__func__, zero_bin, "zero_bin", torch::kInt32, {nf});
+  check_tensor(__func__, resid, "resid", torch::kFloat32, {-1});
+  const int64_t B = resid.numel();
+  check_tensor(__func__, node, "node", torch::kInt32, {B});
+  check_tensor(__func__, node_cnt, "node_cnt", torch::kFloat32, {-1});
+  const int64_t n_nodes = node_cnt.numel();
+  check_tensor(__func__, node_sum, "node_sum", torch::kFloat32, {n_nodes});
+  TORCH_CHECK(nb >= 1 && n_nodes >= 1, __func__, ": nb, n_nodes >= 1");
+  TORCH_CHECK(n_nodes * nb <= HS_LDS_ENTRIES, __func__,
+              ": level too wide for LDS histogram (use the torch path)");
+  check_below_2_31(__func__, {{"B", B}, {"nf", nf}, {"nnz / 4", nnz / 4}});
+  TORCH_CHECK(nf == 0 || B >= 1, __func__, ": entries but no rows");
+  check_on_device(__func__, {feat_ptr, feat_row, feat_bin, feat_idx, zero_bin,
+                  resid,
+                       node, node_cnt, node_sum});
   auto opt = resid.options();
   torch::Tensor cnt = torch::empty({n_nodes, nf, nb}, opt);
   torch::Tensor sum = torch::empty({n_nodes, nf, nb}, opt);
   if (nf == 0) return {cnt, sum};
-  TORCH_CHECK(B >= 1, "gbt_hist_sparse: entries but no rows");
   const int fc = (int)std::min(nf, HS_LDS_ENTRIES / (n_nodes * nb));
   const int64_t n_wg = (nf + fc - 1) / fc;
   const size_t lds = (size_t)2 * n_nodes * fc * nb * sizeof(float);
-  const bool vec4 = nb % 4 == 0 &&
-                    reinterpret_cast<uintptr_t>(cnt.data_ptr<float>()) % 16 == 0 &&
-                    reinterpret_cast<uintptr_t>(sum.data_ptr<float>()) % 16 == 0;
-  hipStream_t st = current_stream();
-#define GO(V)                                                                \
-  hipLaunchKernelGGL((gbt_hist_sparse_kernel<V>), dim3((unsigned)n_wg),      \
-                     dim3(HS_THREADS), lds, st,                              \
-                     feat_ptr.data_ptr<int64_t>(), feat_row.data_ptr<int>(), \
-                     feat_bin.data_ptr<int>(), feat_idx.data_ptr<int>(),     \
-                     zero_bin.data_ptr<int>(), resid.data_ptr<float>(),      \
-                     node.data_ptr<int>(), node_cnt.data_ptr<float>(),       \
-                     node_sum.data_ptr<float>(), cnt.data_ptr<float>(),      \
-                     sum.data_ptr<float>(), (int)B, (int)nf, (int)nb,        \
-                     (int)n_nodes, fc, nnz)
-  if (vec4) GO(true); else GO(false);
-#undef GO
+  const bool vec4 = nb % 4 == 0 && aligned16(cnt.data_ptr<float>()) &&
+                    aligned16(sum.data_ptr<float>());
+  dispatch_bool(vec4, [&](auto v) {
+    hipLaunchKernelGGL(
+        (gbt_hist_sparse_kernel<decltype(v)::value>), dim3((unsigned)n_wg),
+        dim3(HS_THREADS), lds, current_stream(), feat_ptr.data_ptr<int64_t>(),
+        feat_row.data_ptr<int>(), feat_bin.data_ptr<int>(),
+        feat_idx.data_ptr<int>(), zero_bin.data_ptr<int>(),
+        resid.data_ptr<float>(), node.data_ptr<int>(),
+        node_cnt.data_ptr<float>(), node_sum.data_ptr<float>(),
+        cnt.data_ptr<float>(), sum.data_ptr<float>(), (int)B, (int)nf, (int)nb,
+        (int)n_nodes, fc, nnz);
+  });
   return {cnt, sum};
 }

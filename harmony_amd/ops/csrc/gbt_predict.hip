@@ -145,8 +145,6 @@ __global__ __launch_bounds__(PR_THREADS) void gbt_predict_kernel(
   if (live) out[row] = pred;
 }
 
-constexpr int64_t kI31 = (int64_t)1 << 31;
-
 }  // namespace
 
 // The deepest tree K10p takes, and the words of staged trees per LDS group
@@ -163,66 +161,54 @@ torch::Tensor gbt_forest_predict(
     double step_size, int64_t F, c10::optional<torch::Tensor> keys,
     c10::optional<torch::Tensor> key_bin,
     c10::optional<torch::Tensor> row_ptr) {
-  CHECK_IN(forest);
-  TORCH_CHECK(depth >= 1, "gbt_forest_predict: depth must be at least 1");
-  TORCH_CHECK(depth <= PR_MAX_DEPTH,
-              "gbt_forest_predict: tree too deep (use the torch path)");
-  TORCH_CHECK(forest.dtype() == torch::kInt32 && forest.dim() == 2,
-              "forest must be int32 [T, row]");
+  TORCH_CHECK(depth >= 1, __func__, ": depth must be at least 1");
+  TORCH_CHECK(depth <= PR_MAX_DEPTH, __func__,
+              ": tree too deep (use the torch path)");
+  check_tensor(__func__, forest, "forest", torch::kInt32, {-1, -1});
   const bool sparse = !bins.has_value();
   const int64_t ni = ((int64_t)1 << depth) - 1;
   const int64_t base = 1 + 2 * ni + ((int64_t)1 << depth);
   const int64_t extra = sparse ? ni : 0;
   const int64_t T = forest.size(0), row_len = forest.size(1);
   TORCH_CHECK(row_len == base + extra || row_len == base + 2 * ni + extra,
-              "gbt_forest_predict: forest row length does not fit depth");
+              __func__,
+              ": forest row length does not fit depth");
   const bool with_masks = row_len == base + 2 * ni + extra;
-  TORCH_CHECK(F >= 1 && T < kI31, "gbt_forest_predict: F >= 1, T < 2^31");
+  TORCH_CHECK(F >= 1, __func__, ": F must be at least 1");
   int64_t B = 0, nnz = 0;
+  const int64_t *bp = nullptr, *kp = nullptr, *rp = nullptr;
+  const int* kbp = nullptr;
   if (sparse) {
     TORCH_CHECK(keys.has_value() && key_bin.has_value() && row_ptr.has_value(),
-                "sparse input needs keys, key_bin and row_ptr");
-    CHECK_IN(*keys); CHECK_IN(*key_bin); CHECK_IN(*row_ptr);
+                __func__, ": sparse input needs keys, key_bin and row_ptr");
+    kp = check_tensor<int64_t>(__func__, keys, "keys", {-1});
     nnz = keys->numel();
-    TORCH_CHECK(keys->dtype() == torch::kInt64 && keys->dim() == 1,
-                "keys must be int64 [nnz]");
-    TORCH_CHECK(key_bin->dtype() == torch::kInt32 && key_bin->dim() == 1 &&
-                key_bin->numel() == nnz, "key_bin must be int32 [nnz]");
-    TORCH_CHECK(row_ptr->dtype() == torch::kInt64 && row_ptr->dim() == 1 &&
-                row_ptr->numel() >= 1, "row_ptr must be int64 [B+1]");
+    kbp = check_tensor<int>(__func__, key_bin, "key_bin", {nnz});
+    rp = check_tensor<int64_t>(__func__, row_ptr, "row_ptr", {-1});
     B = row_ptr->numel() - 1;
   } else {
-    CHECK_IN(*bins);
-    TORCH_CHECK(bins->dtype() == torch::kInt64 && bins->dim() == 2 &&
-                bins->size(1) == F, "bins must be int64 [B, F]");
+    bp = check_tensor<int64_t>(__func__, bins, "bins", {-1, F});
     B = bins->size(0);
   }
-  TORCH_CHECK(B < kI31, "gbt_forest_predict: B must be below 2^31");
+  check_below_2_31(__func__, {{"T", T}, {"B", B}});
+  const int group = (int)(PR_LDS_WORDS / row_len);
+  TORCH_CHECK(group >= 1, __func__, ": a tree does not fit in LDS");
+  if (sparse) check_on_device(__func__, {forest, keys, key_bin, row_ptr});
+  else check_on_device(__func__, {forest, bins});
   torch::Tensor out = torch::zeros(
       {B}, forest.options().dtype(torch::kFloat32));
   if (B == 0 || T == 0) return out;
-  const int group = (int)(PR_LDS_WORDS / row_len);
-  TORCH_CHECK(group >= 1, "gbt_forest_predict: a tree does not fit in LDS");
   const size_t lds = (size_t)group * row_len * sizeof(int);
   const int64_t n_wg = (B + PR_THREADS - 1) / PR_THREADS;
   const int mask_off = with_masks ? (int)base : 0;
   const int zb_off = sparse ? (int)(row_len - ni) : 0;
-  hipStream_t st = current_stream();
-  if (sparse) {
-    hipLaunchKernelGGL((gbt_predict_kernel<true>), dim3((unsigned)n_wg),
-                       dim3(PR_THREADS), lds, st, nullptr,
-                       keys->data_ptr<int64_t>(), key_bin->data_ptr<int>(),
-                       row_ptr->data_ptr<int64_t>(), forest.data_ptr<int>(),
-                       out.data_ptr<float>(), (int)B, F, (int)T, (int)depth,
-                       (int)row_len, mask_off, zb_off, group, nnz,
-                       (float)step_size);
-  } else {
-    hipLaunchKernelGGL((gbt_predict_kernel<false>), dim3((unsigned)n_wg),
-                       dim3(PR_THREADS), lds, st, bins->data_ptr<int64_t>(),
-                       nullptr, nullptr, nullptr, forest.data_ptr<int>(),
-                       out.data_ptr<float>(), (int)B, F, (int)T, (int)depth,
-                       (int)row_len, mask_off, zb_off, group, nnz,
-                       (float)step_size);
-  }
+  dispatch_bool(sparse, [&](auto sp) {
+    hipLaunchKernelGGL((gbt_predict_kernel<decltype(sp)::value>),
+                       dim3((unsigned)n_wg), dim3(PR_THREADS), lds,
+                       current_stream(), bp, kp, kbp, rp,
+                       forest.data_ptr<int>(), out.data_ptr<float>(), (int)B,
+                       F, (int)T, (int)depth, (int)row_len, mask_off, zb_off,
+                       group, nnz, (float)step_size);
+  });
   return out;
 }

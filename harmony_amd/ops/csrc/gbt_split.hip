@@ -173,19 +173,17 @@ __global__ __launch_bounds__(WAVE) void gbt_split_node_kernel(
 // mask int64, gain float32), each [n_nodes].
 std::vector<torch::Tensor> gbt_best_split(torch::Tensor cnt, torch::Tensor s,
                                           torch::Tensor ftype, double lam) {
-  CHECK_IN(cnt); CHECK_IN(s); CHECK_IN(ftype);
-  TORCH_CHECK(cnt.dtype() == torch::kFloat32 && cnt.dim() == 3 &&
-              s.dtype() == torch::kFloat32 && s.sizes() == cnt.sizes(),
-              "cnt and s must be float32 [n_nodes, F, nb]");
+  check_tensor(__func__, cnt, "cnt", torch::kFloat32, {-1, -1, -1});
+  check_tensor(__func__, s, "s", torch::kFloat32, cnt.sizes());
   const int64_t n_nodes = cnt.size(0), F = cnt.size(1), nb = cnt.size(2);
-  TORCH_CHECK(ftype.dtype() == torch::kInt32 && ftype.dim() == 1 &&
-              ftype.numel() == F, "ftype must be int32 [F]");
-  TORCH_CHECK(nb >= 1 && nb <= WAVE, "gbt_best_split: nb must be in 1..64");
-  TORCH_CHECK(n_nodes >= 1 && F >= 1, "gbt_best_split: empty level");
+  check_tensor(__func__, ftype, "ftype", torch::kInt32, {F});
+  TORCH_CHECK(nb >= 1 && nb <= WAVE, __func__, ": nb must be in 1..64");
+  TORCH_CHECK(n_nodes >= 1 && F >= 1, __func__, ": empty level");
   const int64_t fblocks = (F + WAVES - 1) / WAVES;
-  TORCH_CHECK(n_nodes * fblocks < ((int64_t)1 << 31) &&
-              n_nodes * F * nb < ((int64_t)1 << 40),
-              "gbt_best_split: level too large");
+  check_below_2_31(__func__, {{"n_nodes * feature blocks", n_nodes * fblocks}});
+  TORCH_CHECK(n_nodes * F * nb < ((int64_t)1 << 40), __func__,
+              ": level too large");
+  check_on_device(__func__, {cnt, s, ftype});
   auto dev = cnt.device();
   auto i32 = torch::TensorOptions().dtype(torch::kInt32).device(dev);
   auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(dev);

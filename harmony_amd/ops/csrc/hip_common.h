@@ -5,6 +5,8 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include "binding.h"
+
 #define WAVE 64
 
 // The HIP stream torch has current for this thread (per-job streams are set
@@ -12,8 +14,6 @@
 inline hipStream_t current_stream() {
   return c10::hip::getCurrentHIPStream().stream();
 }
-
-#define CHECK_IN(x) TORCH_CHECK((x).is_cuda() && (x).is_contiguous(), #x " must be contiguous on device")
 
 // Full-wave sum: butterfly over 64 lanes; every lane ends with the total.
 __device__ __forceinline__ float wave_reduce_sum(float v) {

@@ -67,10 +67,16 @@ __global__ void lasso_cd_kernel(const float* __restrict__ Xt,
 
 void lasso_cd(torch::Tensor Xt, torch::Tensor r, torch::Tensor w,
               torch::Tensor col_sq, double lam_n) {
-  CHECK_IN(Xt); CHECK_IN(r); CHECK_IN(w); CHECK_IN(col_sq);
+  check_tensor(__func__, Xt, "Xt", torch::kFloat32, {-1, -1});
   const int F = Xt.size(0), B = Xt.size(1);
-  const size_t lds = (B + CD_THREADS / WAVE + 1) * sizeof(float);
-  TORCH_CHECK(lds <= 64 * 1024, "batch too large for LDS-resident residual");
+  check_tensor(__func__, r, "r", torch::kFloat32, {B});
+  check_tensor(__func__, w, "w", torch::kFloat32, {F});
+  check_tensor(__func__, col_sq, "col_sq", torch::kFloat32, {F});
+  check_below_2_31(__func__, {{"F", Xt.size(0)}});
+  const size_t lds = (Xt.size(1) + CD_THREADS / WAVE + 1) * sizeof(float);
+  TORCH_CHECK(lds <= 64 * 1024, __func__,
+              ": batch too large for LDS-resident residual");
+  check_on_device(__func__, {Xt, r, w, col_sq});
   hipLaunchKernelGGL(lasso_cd_kernel, dim3(1), dim3(CD_THREADS), lds,
                      current_stream(), Xt.data_ptr<float>(),
                      r.data_ptr<float>(), w.data_ptr<float>(),

@@ -320,8 +320,6 @@ __global__ __launch_bounds__(T) void lasso_cd_sparse_kernel(
   for (int i = tid; i < B; i += T) r_g[i] = r[i];
 }
 
-constexpr int64_t kI31 = (int64_t)1 << 31;
-
 }  // namespace
 
 // The largest batch the LDS-resident residual admits.
@@ -333,53 +331,35 @@ void lasso_cd_sparse(torch::Tensor feat_ids, torch::Tensor feat_ptr,
                      torch::Tensor feat_row, torch::Tensor feat_val,
                      torch::Tensor y, torch::Tensor w, torch::Tensor col_sq,
                      double lam_n, torch::Tensor r_out, int64_t threads) {
-  CHECK_IN(feat_ids); CHECK_IN(feat_ptr); CHECK_IN(feat_row);
-  CHECK_IN(feat_val); CHECK_IN(y); CHECK_IN(w); CHECK_IN(col_sq);
-  CHECK_IN(r_out);
-  TORCH_CHECK(feat_ids.dtype() == torch::kInt32 && feat_ids.dim() == 1,
-              "feat_ids must be int32 [nf]");
-  TORCH_CHECK(feat_ptr.dtype() == torch::kInt64 && feat_ptr.dim() == 1 &&
-              feat_ptr.numel() == feat_ids.numel() + 1,
-              "feat_ptr must be int64 [nf+1]");
-  TORCH_CHECK(feat_row.dtype() == torch::kInt32 && feat_row.dim() == 1,
-              "feat_row must be int32 [nnz]");
-  TORCH_CHECK(feat_val.dtype() == torch::kFloat32 && feat_val.dim() == 1 &&
-              feat_val.numel() == feat_row.numel(),
-              "feat_val must be float32 [nnz]");
-  TORCH_CHECK(y.dtype() == torch::kFloat32 && y.dim() == 1 &&
-              r_out.dtype() == torch::kFloat32 && r_out.dim() == 1 &&
-              r_out.numel() == y.numel(),
-              "y and r_out must be float32 [B]");
-  TORCH_CHECK(w.dtype() == torch::kFloat32 && w.dim() == 1,
-              "w must be float32 [F]");
-  TORCH_CHECK(col_sq.dtype() == torch::kFloat32 && col_sq.dim() == 1 &&
-              col_sq.numel() == feat_ids.numel(),
-              "col_sq must be float32 [nf]");
-  const int64_t nf = feat_ids.numel(), nnz = feat_row.numel();
-  const int64_t B = y.numel(), F = w.numel();
-  TORCH_CHECK(nf >= 1 && B >= 1, "lasso_cd_sparse: empty batch");
-  TORCH_CHECK(B <= kMaxRows,
-              "batch too large for LDS-resident residual (max ", kMaxRows,
-              " rows)");
-  TORCH_CHECK(nnz < kI31 && F < kI31 && nf < kI31 - 4 * 1024 * kScan,
-              "lasso_cd_sparse: nnz, F and nf must be below 2^31");
+  check_tensor(__func__, feat_ids, "feat_ids", torch::kInt32, {-1});
+  const int64_t nf = feat_ids.numel();
+  check_tensor(__func__, feat_ptr, "feat_ptr", torch::kInt64, {nf + 1});
+  check_tensor(__func__, feat_row, "feat_row", torch::kInt32, {-1});
+  const int64_t nnz = feat_row.numel();
+  check_tensor(__func__, feat_val, "feat_val", torch::kFloat32, {nnz});
+  check_tensor(__func__, y, "y", torch::kFloat32, {-1});
+  const int64_t B = y.numel();
+  check_tensor(__func__, r_out, "r_out", torch::kFloat32, {B});
+  check_tensor(__func__, w, "w", torch::kFloat32, {-1});
+  const int64_t F = w.numel();
+  check_tensor(__func__, col_sq, "col_sq", torch::kFloat32, {nf});
+  TORCH_CHECK(nf >= 1 && B >= 1, __func__, ": empty batch");
+  TORCH_CHECK(B <= kMaxRows, __func__, ": batch too large for LDS-resident "
+              "residual (max ", kMaxRows, " rows)");
+  check_below_2_31(__func__, {{"nnz", nnz}, {"F", F},
+                        {"nf (padded to the scan width)",
+                         nf + 4 * 1024 * kScan}});
+  check_pow2<64, 1024, 4>(__func__, "threads", threads);
+  check_on_device(__func__, {feat_ids, feat_ptr, feat_row, feat_val, y, w,
+                             col_sq, r_out});
   const size_t lds = (size_t)(kResidOff + B) * sizeof(float);
-  hipStream_t st = current_stream();
-#define GO(TV)                                                              \
-  case TV:                                                                  \
-    hipLaunchKernelGGL((lasso_cd_sparse_kernel<TV>), dim3(1), dim3(TV),     \
-                       lds, st, feat_ids.data_ptr<int>(),                   \
-                       feat_ptr.data_ptr<int64_t>(),                        \
-                       feat_row.data_ptr<int>(),                            \
-                       feat_val.data_ptr<float>(), y.data_ptr<float>(),     \
-                       w.data_ptr<float>(), col_sq.data_ptr<float>(),       \
-                       (float)lam_n, r_out.data_ptr<float>(), (int)B,       \
-                       (int)F, (int)nf, (int)nnz);                          \
-    break
-  switch (threads) {
-    GO(64); GO(256); GO(1024);
-    default:
-      TORCH_CHECK(false, "threads must be 64, 256 or 1024");
-  }
-#undef GO
+  dispatch_pow2<64, 1024, 4>(__func__, "threads", threads, [&](auto t) {
+    hipLaunchKernelGGL(
+        (lasso_cd_sparse_kernel<t.value>), dim3(1), dim3(t.value), lds,
+        current_stream(), feat_ids.data_ptr<int>(),
+        feat_ptr.data_ptr<int64_t>(), feat_row.data_ptr<int>(),
+        feat_val.data_ptr<float>(), y.data_ptr<float>(), w.data_ptr<float>(),
+        col_sq.data_ptr<float>(), (float)lam_n, r_out.data_ptr<float>(),
+        (int)B, (int)F, (int)nf, (int)nnz);
+  });
 }

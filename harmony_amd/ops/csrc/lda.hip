@@ -185,12 +185,26 @@ __global__ void lda_apply_all_kernel(int* __restrict__ shard,
 
 }  // namespace
 
+static int64_t check_apply(const char* op, const torch::Tensor& shard,
+                           const torch::Tensor& rows,
+                           const torch::Tensor& old_t,
+                           const torch::Tensor& new_t) {
+  check_tensor(op, shard, "shard", torch::kInt32, {-1, -1});
+  check_tensor(op, rows, "rows", torch::kInt64, {-1});
+  const int64_t n = rows.size(0);
+  check_tensor(op, old_t, "old_t", torch::kInt32, {n});
+  check_tensor(op, new_t, "new_t", torch::kInt32, {n});
+  check_below_2_31(op, {{"K", shard.size(1)}});
+  return n;
+}
+
 void lda_apply_all(torch::Tensor shard, torch::Tensor word_rows,
                    torch::Tensor old_t, torch::Tensor new_t,
                    int64_t summary_row) {
-  CHECK_IN(shard); CHECK_IN(word_rows); CHECK_IN(old_t); CHECK_IN(new_t);
-  TORCH_CHECK(shard.dtype() == torch::kInt32);
-  const int64_t n = word_rows.size(0);
+  const int64_t n = check_apply(__func__, shard, word_rows, old_t, new_t);
+  TORCH_CHECK(summary_row >= 0 && summary_row < shard.size(0), __func__,
+              ": summary_row must be a row of shard, got ", summary_row);
+  check_on_device(__func__, {shard, word_rows, old_t, new_t});
   if (n == 0) return;
   const int K = shard.size(1);
   const unsigned nblk = (unsigned)std::min<int64_t>((n + 255) / 256, 1024);
@@ -204,9 +218,8 @@ void lda_apply_all(torch::Tensor shard, torch::Tensor word_rows,
 
 void lda_apply_pairs(torch::Tensor shard, torch::Tensor rows,
                      torch::Tensor old_t, torch::Tensor new_t) {
-  CHECK_IN(shard); CHECK_IN(rows); CHECK_IN(old_t); CHECK_IN(new_t);
-  TORCH_CHECK(shard.dtype() == torch::kInt32);
-  const int64_t n = rows.size(0);
+  const int64_t n = check_apply(__func__, shard, rows, old_t, new_t);
+  check_on_device(__func__, {shard, rows, old_t, new_t});
   if (n == 0) return;
   const int K = shard.size(1);
   dim3 blk(256), grid((unsigned)((n + 255) / 256));
@@ -220,12 +233,20 @@ torch::Tensor lda_gibbs(torch::Tensor doc_topic, torch::Tensor word_topic,
                         torch::Tensor word_ids, torch::Tensor assignments,
                         double alpha, double beta, int64_t num_vocabs,
                         int64_t seed) {
-  CHECK_IN(doc_topic); CHECK_IN(word_topic); CHECK_IN(topic_sum);
-  CHECK_IN(doc_offsets); CHECK_IN(word_ids); CHECK_IN(assignments);
-  TORCH_CHECK(doc_topic.dtype() == torch::kInt32);
-  TORCH_CHECK(word_topic.dtype() == torch::kInt32);
-  const int D = doc_topic.size(0), K = doc_topic.size(1);
-  TORCH_CHECK(K <= WAVE * MAXC, "num_topics > ", WAVE * MAXC, " unsupported");
+  check_tensor(__func__, doc_topic, "doc_topic", torch::kInt32, {-1, -1});
+  const int64_t D = doc_topic.size(0), K = doc_topic.size(1);
+  TORCH_CHECK(K <= WAVE * MAXC, __func__, ": num_topics > ", WAVE * MAXC,
+              " unsupported");
+  check_tensor(__func__, word_topic, "word_topic", torch::kInt32, {-1, K});
+  check_tensor(__func__, topic_sum, "topic_sum", torch::kInt32, {K});
+  check_tensor(__func__, doc_offsets, "doc_offsets", torch::kInt64, {D + 1});
+  check_tensor(__func__, word_ids, "word_ids", torch::kInt64, {-1});
+  check_tensor(__func__, assignments, "assignments", torch::kInt32,
+               {word_ids.numel()});
+  check_below_2_31(__func__, {{"D", D}});
+  check_on_device(__func__, {doc_topic, word_topic, topic_sum, doc_offsets,
+                  word_ids,
+                       assignments});
   if (D == 0) return assignments;
   int G = (K <= 32 * MAXC) ? 32 : 64;             // 2 docs/wave when K fits
   const char* env = getenv("HARMONY_LDA_G");      // A/B override
@@ -236,8 +257,8 @@ torch::Tensor lda_gibbs(torch::Tensor doc_topic, torch::Tensor word_topic,
   dim3 blk(BLOCK_THREADS);
   dim3 grid((D + groups - 1) / groups);
   const size_t shmem = (size_t)(groups * K + K) * 4;
-  if (G == 16) {
-    hipLaunchKernelGGL(lda_gibbs_kernel<16>, grid, blk, shmem,
+  dispatch_pow2<16, 64>(__func__, "lanes per document", G, [&](auto g) {
+    hipLaunchKernelGGL(lda_gibbs_kernel<g.value>, grid, blk, shmem,
                        current_stream(),
                        doc_topic.data_ptr<int>(), word_topic.data_ptr<int>(),
                        topic_sum.data_ptr<int>(),
@@ -245,30 +266,8 @@ torch::Tensor lda_gibbs(torch::Tensor doc_topic, torch::Tensor word_topic,
                        word_ids.data_ptr<int64_t>(),
                        assignments.data_ptr<int>(),
                        (float)alpha, (float)beta,
-                       (float)(num_vocabs * beta), D, K,
+                       (float)(num_vocabs * beta), (int)D, (int)K,
                        (unsigned int)(seed & 0xffffffff));
-  } else if (G == 32) {
-    hipLaunchKernelGGL(lda_gibbs_kernel<32>, grid, blk, shmem,
-                       current_stream(),
-                       doc_topic.data_ptr<int>(), word_topic.data_ptr<int>(),
-                       topic_sum.data_ptr<int>(),
-                       doc_offsets.data_ptr<int64_t>(),
-                       word_ids.data_ptr<int64_t>(),
-                       assignments.data_ptr<int>(),
-                       (float)alpha, (float)beta,
-                       (float)(num_vocabs * beta), D, K,
-                       (unsigned int)(seed & 0xffffffff));
-  } else {
-    hipLaunchKernelGGL(lda_gibbs_kernel<64>, grid, blk, shmem,
-                       current_stream(),
-                       doc_topic.data_ptr<int>(), word_topic.data_ptr<int>(),
-                       topic_sum.data_ptr<int>(),
-                       doc_offsets.data_ptr<int64_t>(),
-                       word_ids.data_ptr<int64_t>(),
-                       assignments.data_ptr<int>(),
-                       (float)alpha, (float)beta,
-                       (float)(num_vocabs * beta), D, K,
-                       (unsigned int)(seed & 0xffffffff));
-  }
+  });
   return assignments;
 }

@@ -765,15 +765,37 @@ torch::Tensor launch_legacy_mh(bool wave, torch::Tensor doc_topic,
                                torch::Tensor word_ids,
                                torch::Tensor assignments,
                                double alpha, double beta, int64_t seed) {
-  CHECK_IN(doc_topic); CHECK_IN(word_topic); CHECK_IN(invden);
-  CHECK_IN(prob); CHECK_IN(alias); CHECK_IN(top_prob); CHECK_IN(top_alias);
-  CHECK_IN(qv); CHECK_IN(doc_offsets); CHECK_IN(word_ids);
-  CHECK_IN(assignments);
-  const int D = doc_topic.size(0), K = doc_topic.size(1);
+  const char* op = wave ? "lda_mh_wave" : "lda_mh";
+  check_tensor(op, doc_topic, "doc_topic", torch::kInt32, {-1, -1});
+  const int64_t D = doc_topic.size(0), K = doc_topic.size(1);
+  TORCH_CHECK(K >= WAVE && K % WAVE == 0, op,
+              ": doc_topic needs K % 64 == 0, got K = ", K);
+  check_tensor(op, prob, "prob", torch::kFloat32, {-1, K});
+  const int64_t rows = prob.size(0);
+  check_tensor(op, alias, "alias", torch::kInt32, {rows, K});
+  check_tensor(op, top_prob, "top_prob", torch::kFloat32, {rows, WAVE});
+  check_tensor(op, top_alias, "top_alias", torch::kInt32, {rows, WAVE});
+  check_tensor(op, qv, "qv", torch::kFloat32, {rows, K});
+  check_tensor(op, word_topic, "word_topic", torch::kInt32, {-1, K});
+  TORCH_CHECK(word_topic.size(0) >= rows, op,
+              ": word_topic has fewer rows than the tables");
+  check_tensor(op, invden, "invden", torch::kFloat32, {K});
+  check_tensor(op, doc_offsets, "doc_offsets", torch::kInt64, {D + 1});
+  check_tensor(op, word_ids, "word_ids", torch::kInt64, {-1});
+  check_tensor(op, assignments, "assignments", torch::kInt32,
+               {word_ids.numel()});
+  check_below_2_31(op, {{"D", D}});
+  int threads = ALIAS_THREADS;    // HARMONY_LDA_MH_THREADS: fill/LDS A/B
+  const char* te = getenv("HARMONY_LDA_MH_THREADS");
+  if (te) { int t = atoi(te); if (t==64 || t==128 || t==256) threads = t; }
+  TORCH_CHECK(wave || (size_t)threads * K <= 160 * 1024, op,
+              ": K too large for u8 LDS rows");
+  check_on_device(op, {doc_topic, word_topic, invden, prob, alias, top_prob,
+                       top_alias, qv, doc_offsets, word_ids, assignments});
   if (D == 0) return assignments;
   const LegacyTables tv{prob.data_ptr<float>(), alias.data_ptr<int>(),
                         top_prob.data_ptr<float>(), top_alias.data_ptr<int>(),
-                        qv.data_ptr<float>(), K, K / WAVE};
+                        qv.data_ptr<float>(), (int)K, (int)(K / WAVE)};
   const unsigned int seed32 = (unsigned int)(seed & 0xffffffff);
   if (wave) {
     int waves_wg = 4;                    // 256 threads, 4 docs per block
@@ -788,15 +810,11 @@ torch::Tensor launch_legacy_mh(bool wave, torch::Tensor doc_topic,
                        word_ids.data_ptr<int64_t>(),
                        assignments.data_ptr<int>(), (int*)nullptr,
                        (const int*)nullptr, (int64_t)0,
-                       (float)alpha, (float)beta, D, seed32);
+                       (float)alpha, (float)beta, (int)D, seed32);
     return assignments;
   }
-  int threads = ALIAS_THREADS;    // HARMONY_LDA_MH_THREADS: fill/LDS A/B
-  const char* te = getenv("HARMONY_LDA_MH_THREADS");
-  if (te) { int t = atoi(te); if (t==64 || t==128 || t==256) threads = t; }
   dim3 blk(threads), grid((D + threads - 1) / threads);
   const size_t shmem = (size_t)threads * K;           // u8 rows
-  TORCH_CHECK(shmem <= 160 * 1024, "K too large for u8 LDS rows");
   const char* pe = getenv("HARMONY_LDA_MH_PREFETCH");
   const bool pf = !(pe && atoi(pe) == 0);   // default: prefetch on
   auto kern = pf ? lda_mh_kernel<true> : lda_mh_kernel<false>;
@@ -806,7 +824,7 @@ torch::Tensor launch_legacy_mh(bool wave, torch::Tensor doc_topic,
                      doc_offsets.data_ptr<int64_t>(),
                      word_ids.data_ptr<int64_t>(),
                      assignments.data_ptr<int>(),
-                     (float)alpha, (float)beta, D, seed32);
+                     (float)alpha, (float)beta, (int)D, seed32);
   return assignments;
 }
 
@@ -817,10 +835,13 @@ int64_t lda_alias_build_batch() { return BUILD_BATCH; }
 std::vector<torch::Tensor> lda_alias_build(
     torch::Tensor word_topic, torch::Tensor topic_sum, double beta,
     int64_t num_vocabs, c10::optional<int64_t> max_workgroups) {
-  CHECK_IN(word_topic); CHECK_IN(topic_sum);
-  TORCH_CHECK(word_topic.dtype() == torch::kInt32);
-  const int rows = word_topic.size(0), K = word_topic.size(1);
-  TORCH_CHECK(K % WAVE == 0, "alias sampler requires K % 64 == 0");
+  check_tensor(__func__, word_topic, "word_topic", torch::kInt32, {-1, -1});
+  const int64_t rows = word_topic.size(0), K = word_topic.size(1);
+  TORCH_CHECK(K % WAVE == 0, __func__, ": alias sampler requires K % 64 == 0");
+  check_tensor(__func__, topic_sum, "topic_sum", topic_sum.scalar_type(), {K});
+  check_below_2_31(__func__, {{"rows", rows}});
+  const BuildLaunch L(rows, K, max_workgroups);
+  check_on_device(__func__, {word_topic, topic_sum});
   auto invden = build_invden(topic_sum, beta, num_vocabs);
   auto prob = torch::empty({rows, K},
                            word_topic.options().dtype(torch::kFloat32));
@@ -832,14 +853,13 @@ std::vector<torch::Tensor> lda_alias_build(
                          word_topic.options().dtype(torch::kFloat32));
   auto qsum = torch::empty({rows}, prob.options());
   if (rows > 0) {
-    const BuildLaunch L(rows, K, max_workgroups);
     const LegacyOut out{word_topic.data_ptr<int>(), prob.data_ptr<float>(),
                         alias.data_ptr<int>(), top_prob.data_ptr<float>(),
                         top_alias.data_ptr<int>(), qv.data_ptr<float>(),
-                        qsum.data_ptr<float>(), K};
+                        qsum.data_ptr<float>(), (int)K};
     hipLaunchKernelGGL(alias_build_kernel, L.grid, L.blk, L.shmem,
                        current_stream(), out, invden.data_ptr<float>(),
-                       (float)beta, rows);
+                       (float)beta, (int)rows);
   }
   return {prob, alias, top_prob, top_alias, qv, qsum, invden};
 }
@@ -871,40 +891,14 @@ torch::Tensor lda_mh_wave(torch::Tensor doc_topic, torch::Tensor word_topic,
 
 // ---- K7d host entries: packed tables ----
 
-#define LDA_DISPATCH_S(S_, ...)                                     \
-  switch (S_) {                                                     \
-    case 1: { constexpr int S = 1; __VA_ARGS__; break; }            \
-    case 2: { constexpr int S = 2; __VA_ARGS__; break; }            \
-    case 4: { constexpr int S = 4; __VA_ARGS__; break; }            \
-    case 8: { constexpr int S = 8; __VA_ARGS__; break; }            \
-    default: TORCH_CHECK(false, "packed LDA tables need K/64 in {1,2,4,8}"); \
-  }
-
-static int packed_S(const torch::Tensor& rec, const torch::Tensor& top) {
-  CHECK_IN(rec); CHECK_IN(top);
-  TORCH_CHECK(rec.dtype() == torch::kInt32 && top.dtype() == torch::kInt32);
-  TORCH_CHECK(rec.dim() == 3 && rec.size(1) == WAVE && rec.size(2) % 4 == 0,
-              "rec must be [rows][64][4*S] int32");
-  TORCH_CHECK(top.dim() == 3 && top.size(0) == rec.size(0) &&
-              top.size(1) == WAVE && top.size(2) == 2,
-              "top must be [rows][64][2] int32");
+// rec int32 [rows][64][4*S], top int32 [rows][64][2]; returns S = K / 64.
+static int packed_S(const char* op, const torch::Tensor& rec,
+                    const torch::Tensor& top) {
+  check_tensor(op, rec, "rec", torch::kInt32, {-1, WAVE, -1});
+  TORCH_CHECK(rec.size(2) % 4 == 0, op, ": rec must be [rows][64][4*S] int32");
+  check_tensor(op, top, "top", torch::kInt32, {rec.size(0), WAVE, 2});
+  check_below_2_31(op, {{"rows", rec.size(0)}});
   return (int)(rec.size(2) / 4);
-}
-
-static const int* check_rows(const c10::optional<torch::Tensor>& src_rows,
-                             const torch::Tensor& src, int64_t rows, int K) {
-  CHECK_IN(src);
-  TORCH_CHECK(src.dtype() == torch::kInt32 && src.dim() == 2 &&
-              src.size(1) == K, "src must be [n][K] int32");
-  if (!src_rows.has_value()) {
-    TORCH_CHECK(src.size(0) >= rows, "src has fewer rows than rec");
-    return nullptr;
-  }
-  const torch::Tensor& r = *src_rows;
-  CHECK_IN(r);
-  TORCH_CHECK(r.dtype() == torch::kInt32 && r.dim() == 1 &&
-              r.size(0) == rows, "src_rows must be [rows] int32");
-  return r.data_ptr<int>();
 }
 
 std::vector<torch::Tensor> lda_alias_build_packed(
@@ -912,22 +906,29 @@ std::vector<torch::Tensor> lda_alias_build_packed(
     torch::Tensor topic_sum, double beta, int64_t num_vocabs,
     torch::Tensor rec, torch::Tensor top,
     c10::optional<int64_t> max_workgroups) {
-  CHECK_IN(topic_sum);
-  const int S_ = packed_S(rec, top);
+  const int S_ = packed_S(__func__, rec, top);
   const int rows = rec.size(0), K = S_ * WAVE;
-  TORCH_CHECK(topic_sum.numel() == K);
-  const int* rows_p = check_rows(src_rows, src, rows, K);
+  check_tensor(__func__, topic_sum, "topic_sum", topic_sum.scalar_type(), {K});
+  check_tensor(__func__, src, "src", torch::kInt32, {-1, K});
+  const int* rows_p = check_tensor<int>(__func__, src_rows, "src_rows", {rows});
+  TORCH_CHECK(rows_p != nullptr || src.size(0) >= rows, __func__,
+              ": src has fewer rows than rec");
+  check_pow2<1, 8>(__func__, "K / 64", S_);
+  const BuildLaunch L(rows, K, max_workgroups);
+  check_on_device(__func__, {src, src_rows, topic_sum, rec, top});
   auto invden = build_invden(topic_sum, beta, num_vocabs);
   auto qsum = torch::empty({rows}, invden.options());
   if (rows > 0) {
-    const BuildLaunch L(rows, K, max_workgroups);
-    LDA_DISPATCH_S(S_, hipLaunchKernelGGL(
-        alias_build_packed_kernel<S>, L.grid, L.blk, L.shmem,
-        current_stream(),
-        PackedOut<S>{src.data_ptr<int>(), rows_p, rec.data_ptr<int>(),
-                     reinterpret_cast<int2*>(top.data_ptr<int>()),
-                     qsum.data_ptr<float>()},
-        invden.data_ptr<float>(), (float)beta, rows));
+    dispatch_pow2<1, 8>(__func__, "K / 64", S_, [&](auto s) {
+      constexpr int S = decltype(s)::value;
+      hipLaunchKernelGGL(
+          alias_build_packed_kernel<S>, L.grid, L.blk, L.shmem,
+          current_stream(),
+          PackedOut<S>{src.data_ptr<int>(), rows_p, rec.data_ptr<int>(),
+                       reinterpret_cast<int2*>(top.data_ptr<int>()),
+                       qsum.data_ptr<float>()},
+          invden.data_ptr<float>(), (float)beta, rows);
+    });
   }
   return {invden, qsum};
 }
@@ -942,52 +943,51 @@ torch::Tensor lda_mh_wave_packed(torch::Tensor doc_topic,
                                  c10::optional<torch::Tensor> shard,
                                  c10::optional<torch::Tensor> row_of_local,
                                  int64_t summary_row) {
-  CHECK_IN(doc_topic); CHECK_IN(word_topic); CHECK_IN(invden); CHECK_IN(doc_offsets);
-  CHECK_IN(word_ids); CHECK_IN(assignments);
-  const int S_ = packed_S(rec, top);
-  const int D = doc_topic.size(0), K = doc_topic.size(1);
-  TORCH_CHECK(K == S_ * WAVE, "doc_topic width does not match rec");
-  TORCH_CHECK(doc_topic.dtype() == torch::kInt32 &&
-              assignments.dtype() == torch::kInt32 &&
-              word_ids.dtype() == torch::kInt32 &&
-              doc_offsets.dtype() == torch::kInt64 &&
-              invden.dtype() == torch::kFloat32 && invden.numel() == K);
-  TORCH_CHECK(doc_offsets.numel() == D + 1 &&
-              word_ids.numel() == assignments.numel());
+  const int S_ = packed_S(__func__, rec, top);
+  const int64_t K = S_ * WAVE;
+  check_tensor(__func__, doc_topic, "doc_topic", torch::kInt32, {-1, K});
+  const int64_t D = doc_topic.size(0);
+  check_tensor(__func__, invden, "invden", torch::kFloat32, {K});
+  check_tensor(__func__, doc_offsets, "doc_offsets", torch::kInt64, {D + 1});
+  check_tensor(__func__, word_ids, "word_ids", torch::kInt32, {-1});
+  check_tensor(__func__, assignments, "assignments", torch::kInt32,
+               {word_ids.numel()});
   const bool fused = shard.has_value();
-  int* shard_p = nullptr; const int* rol_p = nullptr;
-  if (fused) {
-    TORCH_CHECK(row_of_local.has_value(), "fused apply needs row_of_local");
-    CHECK_IN(*shard); CHECK_IN(*row_of_local);
-    TORCH_CHECK(shard->dtype() == torch::kInt32 && shard->dim() == 2 &&
-                shard->size(1) == K);
-    TORCH_CHECK(row_of_local->dtype() == torch::kInt32 &&
-                row_of_local->numel() == rec.size(0));
-    TORCH_CHECK(summary_row >= 0 && summary_row < shard->size(0));
-    shard_p = shard->data_ptr<int>();
-    rol_p = row_of_local->data_ptr<int>();
-  }
-  TORCH_CHECK(word_topic.dtype() == torch::kInt32 &&
-              word_topic.dim() == 2 && word_topic.size(1) == K &&
-              word_topic.size(0) >= rec.size(0),
-              "word_topic must be [>= rec rows][K] int32");
+  TORCH_CHECK(!fused || row_of_local.has_value(), __func__,
+              ": fused apply needs row_of_local");
+  int* shard_p = check_tensor<int>(__func__, shard, "shard", {-1, K});
+  const int* rol_p = !fused ? nullptr :
+      check_tensor<int>(__func__, row_of_local, "row_of_local", {rec.size(0)});
+  TORCH_CHECK(!fused || (summary_row >= 0 && summary_row < shard->size(0)),
+              __func__,
+              ": summary_row must be a row of shard, got ", summary_row);
+  // the table may hold more rows than the batch's tables index
+  check_tensor(__func__, word_topic, "word_topic", torch::kInt32, {-1, K});
+  TORCH_CHECK(word_topic.size(0) >= rec.size(0), __func__,
+              ": word_topic must be [>= rec rows][K] int32");
+  check_pow2<1, 8>(__func__, "K / 64", S_);
+  check_below_2_31(__func__, {{"D", D}});
+  check_on_device(__func__, {doc_topic, word_topic, rec, top, invden,
+                  doc_offsets,
+                       word_ids, assignments, shard, row_of_local});
   if (D == 0) return assignments;
   const int waves_wg = 4;              // 256 threads, 4 docs per block
   dim3 blk(WAVE * waves_wg), grid((D + waves_wg - 1) / waves_wg);
   const size_t shmem = ((size_t)waves_wg + (fused ? 1 : 0)) * K * 4;
-#define LDA_LAUNCH_PACKED(F)                                              \
-  hipLaunchKernelGGL((lda_mh_wave_kernel<PackedTables<S>, F>), grid, blk, \
-                     shmem, current_stream(), doc_topic.data_ptr<int>(),  \
-                     word_topic.data_ptr<int>(), invden.data_ptr<float>(),\
-                     PackedTables<S>{rec.data_ptr<int>(),                 \
-                         reinterpret_cast<const int2*>(top.data_ptr<int>())},\
-                     doc_offsets.data_ptr<int64_t>(),                     \
-                     word_ids.data_ptr<int>(),                            \
-                     assignments.data_ptr<int>(), shard_p, rol_p,         \
-                     summary_row, (float)alpha, (float)beta, D,           \
-                     (unsigned int)(seed & 0xffffffff))
-  LDA_DISPATCH_S(S_, if (fused) LDA_LAUNCH_PACKED(true);
-                     else LDA_LAUNCH_PACKED(false));
-#undef LDA_LAUNCH_PACKED
+  dispatch_pow2<1, 8>(__func__, "K / 64", S_, [&](auto s) {
+    constexpr int S = decltype(s)::value;
+    dispatch_bool(fused, [&](auto f) {
+      hipLaunchKernelGGL(
+          (lda_mh_wave_kernel<PackedTables<S>, decltype(f)::value>), grid, blk,
+          shmem, current_stream(), doc_topic.data_ptr<int>(),
+          word_topic.data_ptr<int>(), invden.data_ptr<float>(),
+          PackedTables<S>{rec.data_ptr<int>(),
+              reinterpret_cast<const int2*>(top.data_ptr<int>())},
+          doc_offsets.data_ptr<int64_t>(), word_ids.data_ptr<int>(),
+          assignments.data_ptr<int>(), shard_p, rol_p, summary_row,
+          (float)alpha, (float)beta, (int)D,
+          (unsigned int)(seed & 0xffffffff));
+    });
+  });
   return assignments;
 }

@@ -186,25 +186,6 @@ lda_foldin_kernel(const int* __restrict__ word_topic,
   if (lane == 0) ll_out[doc] = ll;
 }
 
-template <int G, int NC, int PF, bool FULL>
-void launch(const torch::Tensor& word_topic, const torch::Tensor& topic_sum,
-            const torch::Tensor& obs_ptr, const torch::Tensor& obs_word,
-            const torch::Tensor& obs_cnt, const torch::Tensor& sc_ptr,
-            const torch::Tensor& sc_word, const torch::Tensor& sc_cnt,
-            torch::Tensor& theta, torch::Tensor& ll, float alpha, float beta,
-            float vbeta, int D, int K, int iters) {
-  constexpr int GROUPS = BLOCK_THREADS / G;
-  dim3 blk(BLOCK_THREADS), grid((D + GROUPS - 1) / GROUPS);
-  hipLaunchKernelGGL((lda_foldin_kernel<G, NC, PF, FULL>), grid, blk,
-                     (size_t)K * sizeof(float), current_stream(),
-                     word_topic.data_ptr<int>(), topic_sum.data_ptr<int>(),
-                     obs_ptr.data_ptr<int64_t>(),
-                     obs_word.data_ptr<int64_t>(), obs_cnt.data_ptr<int>(),
-                     sc_ptr.data_ptr<int64_t>(), sc_word.data_ptr<int64_t>(),
-                     sc_cnt.data_ptr<int>(), theta.data_ptr<float>(),
-                     ll.data_ptr<float>(), alpha, beta, vbeta, D, K, iters);
-}
-
 }  // namespace
 
 int64_t lda_foldin_max_topics() { return WAVE * MAXC; }
@@ -217,32 +198,27 @@ std::vector<torch::Tensor> lda_foldin(
     torch::Tensor obs_word, torch::Tensor obs_cnt, torch::Tensor sc_ptr,
     torch::Tensor sc_word, torch::Tensor sc_cnt, double alpha, double beta,
     int64_t num_vocabs, int64_t iters) {
-  CHECK_IN(word_topic); CHECK_IN(topic_sum); CHECK_IN(obs_ptr);
-  CHECK_IN(obs_word); CHECK_IN(obs_cnt); CHECK_IN(sc_ptr); CHECK_IN(sc_word);
-  CHECK_IN(sc_cnt);
-  TORCH_CHECK(word_topic.dtype() == torch::kInt32 && word_topic.dim() == 2);
-  TORCH_CHECK(topic_sum.dtype() == torch::kInt32);
-  TORCH_CHECK(obs_ptr.dtype() == torch::kInt64 &&
-              sc_ptr.dtype() == torch::kInt64);
-  TORCH_CHECK(obs_word.dtype() == torch::kInt64 &&
-              sc_word.dtype() == torch::kInt64);
-  TORCH_CHECK(obs_cnt.dtype() == torch::kInt32 &&
-              sc_cnt.dtype() == torch::kInt32);
+  check_tensor(__func__, word_topic, "word_topic", torch::kInt32, {-1, -1});
   const int64_t K = word_topic.size(1);
-  TORCH_CHECK(K >= 1 && K <= WAVE * MAXC, "num_topics > ", WAVE * MAXC,
+  TORCH_CHECK(K >= 1 && K <= WAVE * MAXC, __func__, ": num_topics > ",
+              WAVE * MAXC,
               " unsupported");
-  TORCH_CHECK(topic_sum.numel() == K, "topic_sum must hold num_topics counts");
-  TORCH_CHECK(num_vocabs >= 1 && num_vocabs < ((int64_t)1 << 31) &&
-              word_topic.size(0) >= num_vocabs,
-              "word_topic has fewer than num_vocabs rows");
-  TORCH_CHECK(obs_ptr.dim() == 1 && obs_ptr.size(0) >= 1 &&
-              sc_ptr.dim() == 1 && sc_ptr.size(0) == obs_ptr.size(0),
-              "obs_ptr and sc_ptr must both be [D + 1]");
-  TORCH_CHECK(obs_cnt.numel() == obs_word.numel() &&
-              sc_cnt.numel() == sc_word.numel());
-  TORCH_CHECK(iters >= 0 && iters < (1 << 30));
+  check_tensor(__func__, topic_sum, "topic_sum", torch::kInt32, {K});
+  check_below_2_31(__func__, {{"num_vocabs", num_vocabs}});
+  TORCH_CHECK(num_vocabs >= 1 && word_topic.size(0) >= num_vocabs, __func__,
+              ": word_topic has fewer than num_vocabs rows");
+  check_tensor(__func__, obs_ptr, "obs_ptr", torch::kInt64, {-1});
   const int64_t D = obs_ptr.size(0) - 1;
-  TORCH_CHECK(D < (int64_t)1 << 31);
+  check_tensor(__func__, sc_ptr, "sc_ptr", torch::kInt64, {D + 1});
+  check_tensor(__func__, obs_word, "obs_word", torch::kInt64, {-1});
+  check_tensor(__func__, obs_cnt, "obs_cnt", torch::kInt32, {obs_word.numel()});
+  check_tensor(__func__, sc_word, "sc_word", torch::kInt64, {-1});
+  check_tensor(__func__, sc_cnt, "sc_cnt", torch::kInt32, {sc_word.numel()});
+  TORCH_CHECK(iters >= 0 && iters < (1 << 30), __func__,
+              ": iters must be in [0, 2^30)");
+  check_below_2_31(__func__, {{"D", D}});
+  check_on_device(__func__, {word_topic, topic_sum, obs_ptr, obs_word, obs_cnt,
+                       sc_ptr, sc_word, sc_cnt});
   auto fopt = word_topic.options().dtype(torch::kFloat32);
   auto theta = torch::empty({D, K}, fopt);
   auto ll = torch::empty({D}, fopt);
@@ -257,32 +233,31 @@ std::vector<torch::Tensor> lda_foldin(
   if (env && atoi(env) == 1) pf = 1;
   if (env && atoi(env) == 2) pf = 2;
 
-#define FOLDIN_LAUNCH(G_, NC_, PF_, FULL_)                                   \
-  launch<G_, NC_, PF_, FULL_>(                                               \
-      word_topic, topic_sum, obs_ptr, obs_word, obs_cnt, sc_ptr, sc_word,    \
-      sc_cnt, theta, ll, (float)alpha, (float)beta,                          \
-      (float)(num_vocabs * beta), (int)D, (int)K, (int)iters)
-#define FOLDIN_FULL(G_, NC_, PF_)                                            \
-  do {                                                                       \
-    if (K == (NC_) * (G_)) FOLDIN_LAUNCH(G_, NC_, PF_, true);                \
-    else FOLDIN_LAUNCH(G_, NC_, PF_, false);                                 \
-  } while (0)
-#define FOLDIN_PF(G_, NC_)                                                   \
-  do {                                                                       \
-    if (pf == 2) FOLDIN_FULL(G_, NC_, 2); else FOLDIN_FULL(G_, NC_, 1);      \
-  } while (0)
-#define FOLDIN_NC(G_)                                                        \
-  switch (nc) {                                                              \
-    case 1: FOLDIN_PF(G_, 1); break;                                         \
-    case 2: FOLDIN_PF(G_, 2); break;                                         \
-    case 4: FOLDIN_PF(G_, 4); break;                                         \
-    case 8: FOLDIN_PF(G_, 8); break;                                         \
-    default: FOLDIN_PF(G_, 16); break;                                       \
+  auto go = [&](auto g, auto c) {
+    constexpr int G_ = decltype(g)::value, NC_ = decltype(c)::value;
+    dispatch_bool(pf == 2, [&](auto pf2) {
+      dispatch_bool(K == NC_ * G_, [&](auto full) {
+        constexpr int PF_ = decltype(pf2)::value ? 2 : 1;
+        hipLaunchKernelGGL(
+            (lda_foldin_kernel<G_, NC_, PF_, decltype(full)::value>),
+            dim3((D + BLOCK_THREADS / G_ - 1) / (BLOCK_THREADS / G_)),
+            dim3(BLOCK_THREADS), (size_t)K * sizeof(float), current_stream(),
+            word_topic.data_ptr<int>(), topic_sum.data_ptr<int>(),
+            obs_ptr.data_ptr<int64_t>(), obs_word.data_ptr<int64_t>(),
+            obs_cnt.data_ptr<int>(), sc_ptr.data_ptr<int64_t>(),
+            sc_word.data_ptr<int64_t>(), sc_cnt.data_ptr<int>(),
+            theta.data_ptr<float>(), ll.data_ptr<float>(), (float)alpha,
+            (float)beta, (float)(num_vocabs * beta), (int)D, (int)K,
+            (int)iters);
+      });
+    });
+  };
+  if (G == 32) {
+    dispatch_pow2<1, 16>(__func__, "chunks per lane", nc, [&](auto c) {
+      go(std::integral_constant<int, 32>{}, c);
+    });
+  } else {                                                 // K > 512
+    go(std::integral_constant<int, 64>{}, std::integral_constant<int, 16>{});
   }
-  if (G == 32) { FOLDIN_NC(32) } else { FOLDIN_PF(64, 16); }   // K > 512
-#undef FOLDIN_NC
-#undef FOLDIN_PF
-#undef FOLDIN_FULL
-#undef FOLDIN_LAUNCH
   return {theta, ll};
 }

@@ -216,9 +216,13 @@ void mlr_grad_kernel(const float* __restrict__ P,
 }  // namespace
 
 torch::Tensor mlr_grad(torch::Tensor P, torch::Tensor X) {
-  CHECK_IN(P); CHECK_IN(X);
-  const int B = X.size(0), F = X.size(1), C = P.size(1);
-  TORCH_CHECK(P.size(0) == B && C <= MLR_MAXC);
+  check_tensor(__func__, X, "X", torch::kFloat32, {-1, -1});
+  const int B = X.size(0), F = X.size(1);
+  check_tensor(__func__, P, "P", torch::kFloat32, {B, -1});
+  const int C = P.size(1);
+  TORCH_CHECK(C <= MLR_MAXC, __func__, ": P supports C <= ", MLR_MAXC);
+  check_below_2_31(__func__, {{"B", X.size(0)}, {"F", X.size(1)}});
+  check_on_device(__func__, {P, X});
   auto grad = torch::zeros({C, F}, X.options());
   if (B > 0) {
     dim3 blk(FWD_THREADS);
@@ -233,11 +237,14 @@ torch::Tensor mlr_grad(torch::Tensor P, torch::Tensor X) {
 
 std::vector<torch::Tensor> mlr_fwd(torch::Tensor X, torch::Tensor W,
                                    torch::Tensor labels) {
-  CHECK_IN(X); CHECK_IN(W); CHECK_IN(labels);
-  TORCH_CHECK(X.dtype() == torch::kFloat32 && W.dtype() == torch::kFloat32);
-  const int B = X.size(0), F = X.size(1), C = W.size(0);
-  TORCH_CHECK(W.size(1) == F, "W must be [C, F]");
-  TORCH_CHECK(C <= MLR_MAXC, "mlr_fwd supports C <= ", MLR_MAXC);
+  check_tensor(__func__, X, "X", torch::kFloat32, {-1, -1});
+  const int B = X.size(0), F = X.size(1);
+  check_tensor(__func__, W, "W", torch::kFloat32, {-1, F});
+  const int C = W.size(0);
+  check_tensor(__func__, labels, "labels", torch::kInt64, {B});
+  TORCH_CHECK(C <= MLR_MAXC, __func__, ": W supports C <= ", MLR_MAXC);
+  check_below_2_31(__func__, {{"B", X.size(0)}, {"F", X.size(1)}});
+  check_on_device(__func__, {X, W, labels});
   auto grad = torch::empty({B, C}, X.options());
   auto loss = torch::zeros({}, X.options());
   auto correct = torch::zeros({}, X.options().dtype(torch::kInt32));
@@ -254,10 +261,11 @@ std::vector<torch::Tensor> mlr_fwd(torch::Tensor X, torch::Tensor W,
 
 std::vector<torch::Tensor> mlr_softmax_grad(torch::Tensor logits,
                                             torch::Tensor labels) {
-  CHECK_IN(logits);
-  CHECK_IN(labels);
-  TORCH_CHECK(logits.dtype() == torch::kFloat32, "logits must be f32");
-  int B = logits.size(0), C = logits.size(1);
+  check_tensor(__func__, logits, "logits", torch::kFloat32, {-1, -1});
+  const int B = logits.size(0), C = logits.size(1);
+  check_tensor(__func__, labels, "labels", torch::kInt64, {B});
+  check_below_2_31(__func__, {{"B", logits.size(0)}, {"C", logits.size(1)}});
+  check_on_device(__func__, {logits, labels});
   auto grad = torch::empty_like(logits);
   auto loss = torch::zeros({}, logits.options());
   auto correct = torch::zeros({}, logits.options().dtype(torch::kInt32));

@@ -196,11 +196,24 @@ void mlr_grad_mfma_kernel(const float* __restrict__ P,   // [B][16]
 // block i+1 overlaps grad of block i, so grad re-reads X from the
 // Infinity Cache while fwd streams the next block from HBM).
 
+// The row window [off, off + n) of a [B, .] batch, whole 64-row tiles.
+static void check_window(const char* op, int64_t off, int64_t n, int64_t B) {
+  TORCH_CHECK(off >= 0 && n >= MT && n % MT == 0 && off + n <= B, op,
+              ": rows [off, off + n) must be 64-row tiles inside the batch of ",
+              B, ", got off = ", off, ", n = ", n);
+  check_below_2_31(op, {{"n", n}});
+}
+
 void mlr_fwd_mfma_part(torch::Tensor X, torch::Tensor Wt, torch::Tensor P,
                        int64_t off, int64_t n, int64_t splitf) {
-  const long F = X.size(1);
+  check_tensor(__func__, X, "X", torch::kFloat32, {-1, -1});
+  const long B = X.size(0), F = X.size(1);
+  check_tensor(__func__, Wt, "Wt", torch::kFloat32, {F, CPAD});
+  check_tensor(__func__, P, "P", torch::kFloat32, {B, CPAD});
+  check_window(__func__, off, n, B);
   const int sf = (int)std::max<int64_t>(1, splitf);
-  TORCH_CHECK(F % ((long)sf * KT) == 0 && n % MT == 0, "fwd part shape");
+  TORCH_CHECK(F % ((long)sf * KT) == 0, __func__, ": F % (splitf*64) != 0");
+  check_on_device(__func__, {X, Wt, P});
   hipLaunchKernelGGL(mlr_fwd_mfma_kernel, dim3(n / MT, sf), dim3(256), 0,
                      current_stream(), X.data_ptr<float>(),
                      Wt.data_ptr<float>(), P.data_ptr<float>(), (int)n, F,
@@ -210,6 +223,14 @@ void mlr_fwd_mfma_part(torch::Tensor X, torch::Tensor Wt, torch::Tensor P,
 void mlr_softmax_part(torch::Tensor P, torch::Tensor labels,
                       torch::Tensor loss, torch::Tensor correct,
                       int64_t off, int64_t n, int64_t C) {
+  check_tensor(__func__, P, "P", torch::kFloat32, {-1, CPAD});
+  const int64_t B = P.size(0);
+  check_tensor(__func__, labels, "labels", torch::kInt64, {B});
+  check_tensor(__func__, loss, "loss", torch::kFloat32, {1});
+  check_tensor(__func__, correct, "correct", torch::kInt32, {1});
+  check_window(__func__, off, n, B);
+  TORCH_CHECK(C >= 1 && C <= CPAD, __func__, ": C must be in 1..16, got ", C);
+  check_on_device(__func__, {P, labels, loss, correct});
   hipLaunchKernelGGL(mlr_softmax_pad_kernel, dim3((n + 255) / 256),
                      dim3(256), 0, current_stream(),
                      P.data_ptr<float>() + off * CPAD,
@@ -221,9 +242,15 @@ void mlr_softmax_part(torch::Tensor P, torch::Tensor labels,
 void mlr_grad_mfma_part(torch::Tensor P, torch::Tensor X,
                         torch::Tensor gradT, int64_t off, int64_t n,
                         int64_t splitb) {
-  const long F = X.size(1);
+  check_tensor(__func__, X, "X", torch::kFloat32, {-1, -1});
+  const long B = X.size(0), F = X.size(1);
+  check_tensor(__func__, P, "P", torch::kFloat32, {B, CPAD});
+  check_tensor(__func__, gradT, "gradT", torch::kFloat32, {CPAD, F});
+  check_window(__func__, off, n, B);
   const int sb = (int)std::max<int64_t>(1, splitb);
-  TORCH_CHECK(n % ((long)sb * KT) == 0, "grad part shape");
+  TORCH_CHECK(n % ((long)sb * KT) == 0, __func__, ": n % (splitb*64) != 0");
+  TORCH_CHECK(F % MT == 0, __func__, ": X needs F % 64 == 0");
+  check_on_device(__func__, {P, X, gradT});
   hipLaunchKernelGGL(mlr_grad_mfma_kernel, dim3(F / MT, sb), dim3(256), 0,
                      current_stream(), P.data_ptr<float>(),
                      X.data_ptr<float>(), gradT.data_ptr<float>(), (int)n,
@@ -238,38 +265,30 @@ std::vector<torch::Tensor> mlr_step_mfma(torch::Tensor X, torch::Tensor Wt,
                                          torch::Tensor labels,
                                          int64_t row_block, int64_t C,
                                          int64_t splitf, int64_t splitb) {
-  CHECK_IN(X); CHECK_IN(Wt); CHECK_IN(labels);
+  check_tensor(__func__, X, "X", torch::kFloat32, {-1, -1});
   const long B = X.size(0), F = X.size(1);
-  TORCH_CHECK(Wt.size(0) == F && Wt.size(1) == CPAD, "Wt must be [F,16]");
-  TORCH_CHECK(C <= CPAD && F % KT == 0 && B % MT == 0,
-              "mlr_step_mfma shape: C<=16, F%64==0, B%64==0");
+  check_tensor(__func__, Wt, "Wt", torch::kFloat32, {F, CPAD});
+  check_tensor(__func__, labels, "labels", torch::kInt64, {B});
+  TORCH_CHECK(B % MT == 0 && F % KT == 0, __func__, ": B, F % 64 != 0");
+  const long rb = row_block > 0 ? row_block : B;
+  TORCH_CHECK(rb % MT == 0, __func__, ": row_block % 64 != 0");
+  TORCH_CHECK(C >= 1 && C <= CPAD && F % (std::max<long>(1, splitf) * KT) == 0
+              && rb % (std::max<long>(1, splitb) * KT) == 0
+              && (B % rb) % (std::max<long>(1, splitb) * KT) == 0, __func__,
+              ": needs 1 <= C <= 16, F % (splitf*64) == 0 and row blocks "
+              "% (splitb*64) == 0");
+  check_on_device(__func__, {X, Wt, labels});
   auto opts = X.options();
   // zeros: the split-F forward accumulates partial logits with atomicAdd
   auto P = torch::zeros({B, (long)CPAD}, opts);
   auto gradT = torch::zeros({(long)CPAD, F}, opts);
   auto loss = torch::zeros({1}, opts);
   auto correct = torch::zeros({1}, opts.dtype(torch::kInt32));
-  hipStream_t s = current_stream();
-
-  long rb = row_block > 0 ? row_block : B;
-  TORCH_CHECK(rb % MT == 0, "row_block % 64 != 0");
   for (long off = 0; off < B; off += rb) {
     const long n = std::min(rb, B - off);
-    const int sf = (int)std::max<long>(1, splitf);
-    TORCH_CHECK(F % ((long)sf * KT) == 0, "F % (splitf*64) != 0");
-    hipLaunchKernelGGL(mlr_fwd_mfma_kernel, dim3(n / MT, sf), dim3(256), 0,
-                       s, X.data_ptr<float>(), Wt.data_ptr<float>(),
-                       P.data_ptr<float>(), (int)n, F, off, sf > 1 ? 1 : 0);
-    hipLaunchKernelGGL(mlr_softmax_pad_kernel, dim3((n + 255) / 256),
-                       dim3(256), 0, s, P.data_ptr<float>() + off * CPAD,
-                       labels.data_ptr<int64_t>() + off,
-                       loss.data_ptr<float>(), correct.data_ptr<int>(),
-                       (int)n, (int)C);
-    const int sb = (int)std::max<long>(1, splitb);
-    TORCH_CHECK(n % ((long)sb * KT) == 0, "rows % (splitb*64) != 0");
-    hipLaunchKernelGGL(mlr_grad_mfma_kernel, dim3(F / MT, sb), dim3(256), 0,
-                       s, P.data_ptr<float>(), X.data_ptr<float>(),
-                       gradT.data_ptr<float>(), (int)n, F, off);
+    mlr_fwd_mfma_part(X, Wt, P, off, n, splitf);
+    mlr_softmax_part(P, labels, loss, correct, off, n, C);
+    mlr_grad_mfma_part(P, X, gradT, off, n, splitb);
   }
   return {gradT, loss, correct};
 }

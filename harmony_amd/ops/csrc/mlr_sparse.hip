@@ -122,32 +122,17 @@ struct GatherArgs {
   int C;
 };
 
-template <int G>
-void launch(dim3 grid, hipStream_t st, const GatherArgs& a) {
-  hipLaunchKernelGGL((mlr_sparse_gather_kernel<G>), grid, dim3(kBlock), 0, st,
-                     a.seg_ptr, a.idx, a.val, a.seg_ids, a.table, a.n_rows,
-                     a.ld, a.out, a.n_out, a.out_seg_stride, a.out_cls_stride,
-                     a.S, a.nnz, a.C);
-}
-
-void run(int64_t group, const GatherArgs& a) {
-  TORCH_CHECK(group >= 1 && group <= 64 && (group & (group - 1)) == 0,
-              "group must be a power of two in 1..64");
+void run(const char* op, int64_t group, const GatherArgs& a) {
   const int64_t segs_per_block = kBlock / group;
-  const int64_t want = (a.S + segs_per_block - 1) / segs_per_block;
-  // memory-bound: cap the grid and let the groups stride over the rest
-  dim3 grid((unsigned)std::min<int64_t>(want, 256 * 8 * 4));
+  const dim3 grid = strided_grid((a.S + segs_per_block - 1) / segs_per_block);
   hipStream_t st = current_stream();
-#define GO(GV) case GV: launch<GV>(grid, st, a); break
-  switch (group) {
-    GO(1); GO(2); GO(4); GO(8); GO(16); GO(32); GO(64);
-  }
-#undef GO
+  dispatch_pow2<1, 64>(op, "group", group, [&](auto g) {
+    hipLaunchKernelGGL((mlr_sparse_gather_kernel<g.value>), grid, dim3(kBlock),
+                       0, st, a.seg_ptr, a.idx, a.val, a.seg_ids, a.table,
+                       a.n_rows, a.ld, a.out, a.n_out, a.out_seg_stride,
+                       a.out_cls_stride, a.S, a.nnz, a.C);
+  });
 }
-
-constexpr int64_t kI31 = (int64_t)1 << 31;
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -157,28 +142,25 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 torch::Tensor mlr_sparse_fwd(torch::Tensor row_ptr, torch::Tensor col,
                              torch::Tensor val, torch::Tensor Wt, int64_t C,
                              int64_t group) {
-  CHECK_IN(row_ptr); CHECK_IN(col); CHECK_IN(val); CHECK_IN(Wt);
-  TORCH_CHECK(row_ptr.dtype() == torch::kInt64 && row_ptr.dim() == 1 &&
-              row_ptr.numel() >= 1, "row_ptr must be int64 [B+1]");
-  TORCH_CHECK(col.dtype() == torch::kInt32 && col.dim() == 1,
-              "col must be int32 [nnz]");
-  TORCH_CHECK(val.dtype() == torch::kFloat32 && val.dim() == 1 &&
-              val.numel() == col.numel(), "val must be float32 [nnz]");
-  TORCH_CHECK(Wt.dtype() == torch::kFloat32 && Wt.dim() == 2,
-              "Wt must be float32 [F, Cp]");
+  check_tensor(__func__, row_ptr, "row_ptr", torch::kInt64, {-1});  // [B+1]
+  check_tensor(__func__, col, "col", torch::kInt32, {-1});
   const int64_t B = row_ptr.numel() - 1, nnz = col.numel();
+  check_tensor(__func__, val, "val", torch::kFloat32, {nnz});
+  check_tensor(__func__, Wt, "Wt", torch::kFloat32, {-1, -1});
   const int64_t F = Wt.size(0), Cp = Wt.size(1);
-  TORCH_CHECK(C >= 1 && Cp % 4 == 0 && Cp >= C && Cp - C < 4,
-              "Wt must be [F, C rounded up to a multiple of 4]");
-  TORCH_CHECK(nnz < kI31 && B < kI31 && F < kI31,
-              "mlr_sparse_fwd: nnz, B and F must be below 2^31");
-  TORCH_CHECK(aligned16(Wt.data_ptr<float>()), "Wt must be 16-byte aligned");
+  TORCH_CHECK(C >= 1 && Cp % 4 == 0 && Cp >= C && Cp - C < 4, __func__,
+              ": Wt must be [F, C rounded up to a multiple of 4]");
+  check_below_2_31(__func__, {{"nnz", nnz}, {"B", B}, {"F", F}});
+  TORCH_CHECK(aligned16(Wt.data_ptr<float>()), __func__,
+              ": Wt must be 16-byte aligned");
+  check_pow2<1, 64>(__func__, "group", group);
+  check_on_device(__func__, {row_ptr, col, val, Wt});
   auto logits = torch::empty({B, C}, Wt.options());
   if (B == 0) return logits;
   GatherArgs a{row_ptr.data_ptr<int64_t>(), col.data_ptr<int>(),
                val.data_ptr<float>(), nullptr, Wt.data_ptr<float>(), F, Cp,
                logits.data_ptr<float>(), B, C, 1, B, nnz, (int)C};
-  run(group, a);
+  run(__func__, group, a);
   return logits;
 }
 
@@ -189,38 +171,29 @@ torch::Tensor mlr_sparse_fwd(torch::Tensor row_ptr, torch::Tensor col,
 torch::Tensor mlr_sparse_grad(torch::Tensor feat_ids, torch::Tensor feat_ptr,
                               torch::Tensor feat_row, torch::Tensor feat_val,
                               torch::Tensor P, int64_t F, int64_t group) {
-  CHECK_IN(feat_ids); CHECK_IN(feat_ptr); CHECK_IN(feat_row);
-  CHECK_IN(feat_val);
-  TORCH_CHECK(P.is_cuda() && P.dtype() == torch::kFloat32 && P.dim() == 2,
-              "P must be float32 [B, C] on device");
-  TORCH_CHECK(feat_ids.dtype() == torch::kInt32 && feat_ids.dim() == 1,
-              "feat_ids must be int32 [nf]");
-  TORCH_CHECK(feat_ptr.dtype() == torch::kInt64 && feat_ptr.dim() == 1 &&
-              feat_ptr.numel() == feat_ids.numel() + 1,
-              "feat_ptr must be int64 [nf+1]");
-  TORCH_CHECK(feat_row.dtype() == torch::kInt32 && feat_row.dim() == 1,
-              "feat_row must be int32 [nnz]");
-  TORCH_CHECK(feat_val.dtype() == torch::kFloat32 && feat_val.dim() == 1 &&
-              feat_val.numel() == feat_row.numel(),
-              "feat_val must be float32 [nnz]");
-  const int64_t nf = feat_ids.numel(), nnz = feat_row.numel();
-  const int64_t B = P.size(0), C = P.size(1);
-  TORCH_CHECK(C >= 1 && F >= 0, "mlr_sparse_grad: need C >= 1, F >= 0");
-  TORCH_CHECK(nnz < kI31 && B < kI31 && F < kI31,
-              "mlr_sparse_grad: nnz, B and F must be below 2^31");
+  check_tensor(__func__, feat_ids, "feat_ids", torch::kInt32, {-1});
+  const int64_t nf = feat_ids.numel();
+  check_tensor(__func__, feat_ptr, "feat_ptr", torch::kInt64, {nf + 1});
+  check_tensor(__func__, feat_row, "feat_row", torch::kInt32, {-1});
+  const int64_t nnz = feat_row.numel();
+  check_tensor(__func__, feat_val, "feat_val", torch::kFloat32, {nnz});
+  check_tensor(__func__, P, "P", torch::kFloat32, {-1, -1}, true);
+  const int64_t B = P.size(0), C = P.size(1), ld = P.stride(0);
+  TORCH_CHECK(C >= 1, __func__, ": P needs C >= 1 classes");
+  check_below_2_31(__func__, {{"nnz", nnz}, {"B", B}, {"F", F}});
+  // 16-byte row loads need every quad of a row inside the row's stride
+  TORCH_CHECK(ld % 4 == 0 && ld >= (C + 3) / 4 * 4 &&
+              aligned16(P.data_ptr<float>()), __func__,
+              ": P must be a 16-byte aligned [B, C] view with a row stride "
+              "that is a multiple of 4 and >= C rounded up to 4");
+  check_pow2<1, 64>(__func__, "group", group);
+  check_on_device(__func__, {feat_ids, feat_ptr, feat_row, feat_val, P});
   auto G = torch::zeros({C, F}, P.options());
   if (nf == 0 || B == 0 || F == 0) return G;
-  // 16-byte row loads need every quad of a row inside the row's stride
-  const int64_t ld = P.stride(0);
-  TORCH_CHECK(P.stride(1) == 1 && ld % 4 == 0 && ld >= (C + 3) / 4 * 4 &&
-              aligned16(P.data_ptr<float>()),
-              "P must be a 16-byte aligned [B, C] view with unit class "
-              "stride and a row stride that is a multiple of 4 and >= C "
-              "rounded up to 4");
   GatherArgs a{feat_ptr.data_ptr<int64_t>(), feat_row.data_ptr<int>(),
                feat_val.data_ptr<float>(), feat_ids.data_ptr<int>(),
                P.data_ptr<float>(), B, ld, G.data_ptr<float>(), F, 1, F, nf,
                nnz, (int)C};
-  run(group, a);
+  run(__func__, group, a);
   return G;
 }

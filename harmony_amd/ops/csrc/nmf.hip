@@ -214,11 +214,21 @@ std::vector<torch::Tensor> nmf_grad_twopass(
     torch::Tensor L, torch::Tensor R, torch::Tensor row_ptr,
     torch::Tensor col_idx, torch::Tensor vals, torch::Tensor perm,
     torch::Tensor seg_ptr, torch::Tensor row_sorted, double lam) {
-  CHECK_IN(L); CHECK_IN(R); CHECK_IN(row_ptr); CHECK_IN(col_idx);
-  CHECK_IN(vals); CHECK_IN(perm); CHECK_IN(seg_ptr); CHECK_IN(row_sorted);
-  const int n = L.size(0), k = L.size(1), m = R.size(0);
-  TORCH_CHECK(k <= 64 * MAXC);
-  TORCH_CHECK(seg_ptr.numel() == m + 1, "seg_ptr must cover all R rows");
+  check_tensor(__func__, L, "L", torch::kFloat32, {-1, -1});
+  const int n = L.size(0), k = L.size(1);
+  check_tensor(__func__, R, "R", torch::kFloat32, {-1, k});
+  const int m = R.size(0);
+  TORCH_CHECK(k <= 64 * MAXC, __func__, ": rank > ", 64 * MAXC, " unsupported");
+  check_tensor(__func__, row_ptr, "row_ptr", torch::kInt64, {L.size(0) + 1});
+  check_tensor(__func__, col_idx, "col_idx", torch::kInt64, {-1});
+  const int64_t nnz = col_idx.numel();
+  check_tensor(__func__, vals, "vals", torch::kFloat32, {nnz});
+  check_tensor(__func__, perm, "perm", torch::kInt64, {nnz});
+  check_tensor(__func__, seg_ptr, "seg_ptr", torch::kInt64, {R.size(0) + 1});
+  check_tensor(__func__, row_sorted, "row_sorted", torch::kInt64, {nnz});
+  check_below_2_31(__func__, {{"n", L.size(0)}, {"m", R.size(0)}});
+  check_on_device(__func__,
+                  {L, R, row_ptr, col_idx, vals, perm, seg_ptr, row_sorted});
   auto lgrad = torch::empty_like(L);
   auto rgrad = torch::empty_like(R);
   auto e = torch::empty_like(vals);
@@ -232,46 +242,26 @@ std::vector<torch::Tensor> nmf_grad_twopass(
   int threads = 256;   // HARMONY_NMF_THREADS: occupancy A/B knob
   const char* te = getenv("HARMONY_NMF_THREADS");
   if (te) { int t = atoi(te); if (t == 128 || t == 256 || t == 512 || t == 1024) threads = t; }
-  if (n > 0) {
-    dim3 grid((n + threads / G - 1) / (threads / G));
-    if (G == 32)
-      hipLaunchKernelGGL(nmf_grad_e_kernel<32>, grid, dim3(threads), 0,
-                         current_stream(),
+  dispatch_pow2<32, 64>(__func__, "lanes per row", G, [&](auto g) {
+    const int per = threads / g.value;
+    if (n > 0)
+      hipLaunchKernelGGL(nmf_grad_e_kernel<g.value>, dim3((n + per - 1) / per),
+                         dim3(threads), 0, current_stream(),
                          L.data_ptr<float>(), R.data_ptr<float>(),
                          row_ptr.data_ptr<int64_t>(),
                          col_idx.data_ptr<int64_t>(),
                          vals.data_ptr<float>(), lgrad.data_ptr<float>(),
                          e.data_ptr<float>(), sqerr.data_ptr<float>(),
                          n, k, 2.f * (float)lam);
-    else
-      hipLaunchKernelGGL(nmf_grad_e_kernel<64>, grid, dim3(threads), 0,
-                         current_stream(),
-                         L.data_ptr<float>(), R.data_ptr<float>(),
-                         row_ptr.data_ptr<int64_t>(),
-                         col_idx.data_ptr<int64_t>(),
-                         vals.data_ptr<float>(), lgrad.data_ptr<float>(),
-                         e.data_ptr<float>(), sqerr.data_ptr<float>(),
-                         n, k, 2.f * (float)lam);
-  }
-  if (m > 0) {
-    dim3 grid((m + threads / G - 1) / (threads / G));
-    if (G == 32)
-      hipLaunchKernelGGL(nmf_rgrad_kernel<32>, grid, dim3(threads), 0,
-                         current_stream(),
+    if (m > 0)
+      hipLaunchKernelGGL(nmf_rgrad_kernel<g.value>, dim3((m + per - 1) / per),
+                         dim3(threads), 0, current_stream(),
                          L.data_ptr<float>(), R.data_ptr<float>(),
                          e.data_ptr<float>(), perm.data_ptr<int64_t>(),
                          seg_ptr.data_ptr<int64_t>(),
                          row_sorted.data_ptr<int64_t>(),
                          rgrad.data_ptr<float>(), m, k, 2.f * (float)lam);
-    else
-      hipLaunchKernelGGL(nmf_rgrad_kernel<64>, grid, dim3(threads), 0,
-                         current_stream(),
-                         L.data_ptr<float>(), R.data_ptr<float>(),
-                         e.data_ptr<float>(), perm.data_ptr<int64_t>(),
-                         seg_ptr.data_ptr<int64_t>(),
-                         row_sorted.data_ptr<int64_t>(),
-                         rgrad.data_ptr<float>(), m, k, 2.f * (float)lam);
-  }
+  });
   return {lgrad, rgrad, sqerr};
 }
 
@@ -279,12 +269,15 @@ std::vector<torch::Tensor> nmf_grad(torch::Tensor L, torch::Tensor R,
                                     torch::Tensor row_ptr,
                                     torch::Tensor col_idx, torch::Tensor vals,
                                     double lam) {
-  CHECK_IN(L); CHECK_IN(R); CHECK_IN(row_ptr); CHECK_IN(col_idx); CHECK_IN(vals);
-  TORCH_CHECK(L.dtype() == torch::kFloat32 && R.dtype() == torch::kFloat32);
-  TORCH_CHECK(L.size(1) == R.size(1), "rank mismatch");
-  TORCH_CHECK(L.size(1) <= 64 * MAXC, "rank > ", 64 * MAXC, " unsupported");
+  check_tensor(__func__, L, "L", torch::kFloat32, {-1, -1});
   const int n = L.size(0), k = L.size(1);
-  TORCH_CHECK(row_ptr.numel() == n + 1, "row_ptr size");
+  check_tensor(__func__, R, "R", torch::kFloat32, {-1, k});
+  TORCH_CHECK(k <= 64 * MAXC, __func__, ": rank > ", 64 * MAXC, " unsupported");
+  check_tensor(__func__, row_ptr, "row_ptr", torch::kInt64, {L.size(0) + 1});
+  check_tensor(__func__, col_idx, "col_idx", torch::kInt64, {-1});
+  check_tensor(__func__, vals, "vals", torch::kFloat32, {col_idx.numel()});
+  check_below_2_31(__func__, {{"n", L.size(0)}});
+  check_on_device(__func__, {L, R, row_ptr, col_idx, vals});
   auto lgrad = torch::empty_like(L);
   auto rgrad = torch::zeros_like(R);
   auto sqerr = torch::zeros({}, L.options());
@@ -594,30 +587,6 @@ nmf_step_b_kernel(const float* __restrict__ L,      // batch rows [n, k]
   io.store(rgrad + (size_t)colid * k, out);
 }
 
-inline bool aligned16(const void* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-}
-
-template <int G, int D, int U, bool VEC>
-void launch_nmf_step(const float* L, const float* Rsrc, const int* row_ptr,
-                     const int* col, const float* vals, const float* step,
-                     const int* perm, const int* seg_ptr,
-                     const int* row_sorted, const int* rsrc_of, float* e,
-                     float* L_new, float* lgrad, float* rgrad, float* sqerr,
-                     int n, int m, int k, float lam2, float max_val) {
-  constexpr int threads = 256, per = threads / G;
-  if (n > 0)
-    hipLaunchKernelGGL((nmf_step_a_kernel<G, D, U, VEC>),
-                       dim3((n + per - 1) / per), dim3(threads), 0,
-                       current_stream(), L, Rsrc, row_ptr, col, vals, step,
-                       e, L_new, lgrad, sqerr, n, k, lam2, max_val);
-  if (m > 0)
-    hipLaunchKernelGGL((nmf_step_b_kernel<G, D, VEC>),
-                       dim3((m + per - 1) / per), dim3(threads), 0,
-                       current_stream(), L, Rsrc, e, perm, seg_ptr,
-                       row_sorted, rsrc_of, rgrad, m, k, lam2);
-}
-
 }  // namespace
 
 // L: [NL, k], the batch is rows l_lo..l_lo+n. col indexes rows of R_src;
@@ -630,34 +599,29 @@ std::vector<torch::Tensor> nmf_step(
     torch::Tensor perm, torch::Tensor seg_ptr, torch::Tensor row_sorted,
     c10::optional<torch::Tensor> rsrc_of, torch::Tensor step, double lam,
     double max_val, bool want_lgrad) {
-  CHECK_IN(L); CHECK_IN(R_src); CHECK_IN(row_ptr); CHECK_IN(col);
-  CHECK_IN(vals); CHECK_IN(perm); CHECK_IN(seg_ptr); CHECK_IN(row_sorted);
-  CHECK_IN(step);
-  TORCH_CHECK(L.dtype() == torch::kFloat32 && R_src.dtype() == torch::kFloat32
-              && vals.dtype() == torch::kFloat32
-              && step.dtype() == torch::kFloat32 && step.numel() == 1);
-  for (const auto& t : {row_ptr, col, perm, seg_ptr, row_sorted})
-    TORCH_CHECK(t.dtype() == torch::kInt32, "nmf_step takes int32 indices");
+  check_tensor(__func__, L, "L", torch::kFloat32, {-1, -1});
   const int k = L.size(1);
-  TORCH_CHECK(R_src.size(1) == k, "rank mismatch");
-  TORCH_CHECK(k >= 1 && k <= 64 * MAXC, "rank > ", 64 * MAXC, " unsupported");
-  TORCH_CHECK(l_lo >= 0 && n >= 0 && l_lo + n <= L.size(0), "L range");
-  TORCH_CHECK(row_ptr.numel() == n + 1, "row_ptr size");
+  check_tensor(__func__, R_src, "R_src", torch::kFloat32, {-1, L.size(1)});
+  TORCH_CHECK(k >= 1 && k <= 64 * MAXC, __func__, ": rank > ", 64 * MAXC,
+              " unsupported");
+  TORCH_CHECK(l_lo >= 0 && n >= 0 && l_lo + n <= L.size(0), __func__,
+              ": rows l_lo..l_lo+n must lie inside L");
+  check_tensor(__func__, row_ptr, "row_ptr", torch::kInt32, {n + 1});
+  check_tensor(__func__, col, "col", torch::kInt32, {-1});
   const int64_t nnz = col.numel();
-  TORCH_CHECK(vals.numel() == nnz && perm.numel() == nnz &&
-              row_sorted.numel() == nnz, "nnz mismatch");
-  TORCH_CHECK(nnz < (int64_t{1} << 31), "nmf_step: nnz must fit int32");
+  check_tensor(__func__, vals, "vals", torch::kFloat32, {nnz});
+  check_tensor(__func__, perm, "perm", torch::kInt32, {nnz});
+  check_tensor(__func__, seg_ptr, "seg_ptr", torch::kInt32, {-1});
   const int m = seg_ptr.numel() - 1;
-  TORCH_CHECK(m >= 0, "seg_ptr size");
-  const int* rsrc_p = nullptr;
-  if (rsrc_of.has_value()) {
-    CHECK_IN(*rsrc_of);
-    TORCH_CHECK(rsrc_of->dtype() == torch::kInt32 && rsrc_of->numel() == m,
-                "rsrc_of: one int32 per rgrad row");
-    rsrc_p = rsrc_of->data_ptr<int>();
-  } else {
-    TORCH_CHECK(R_src.size(0) >= m, "R_src rows < seg_ptr segments");
-  }
+  check_tensor(__func__, row_sorted, "row_sorted", torch::kInt32, {nnz});
+  check_tensor(__func__, step, "step", torch::kFloat32, step.sizes());
+  TORCH_CHECK(step.numel() == 1, __func__, ": step must hold one float");
+  check_below_2_31(__func__, {{"nnz", nnz}, {"n", n}, {"m", m}});
+  const int* rsrc_p = check_tensor<int>(__func__, rsrc_of, "rsrc_of", {m});
+  TORCH_CHECK(rsrc_p != nullptr || R_src.size(0) >= m, __func__,
+              ": R_src has fewer rows than seg_ptr has segments");
+  check_on_device(__func__, {L, R_src, row_ptr, col, vals, perm, seg_ptr,
+                       row_sorted, step, rsrc_of});
   auto L_new = torch::empty({n, k}, L.options());
   auto rgrad = torch::empty({m, k}, L.options());
   auto e = torch::empty({nnz}, L.options());
@@ -668,22 +632,33 @@ std::vector<torch::Tensor> nmf_step(
   const float* Rp = R_src.data_ptr<float>();
   const bool vec = k % 4 == 0 && aligned16(Lp) && aligned16(Rp);
   const bool wide = k > 4 * 32;   // four floats per lane: G=32 holds 128
-#define NMF_STEP_LAUNCH(G, D, U, VEC)                                        \
-  launch_nmf_step<G, D, U, VEC>(                                             \
-      Lp, Rp, row_ptr.data_ptr<int>(), col.data_ptr<int>(),                  \
-      vals.data_ptr<float>(), step.data_ptr<float>(), perm.data_ptr<int>(),  \
-      seg_ptr.data_ptr<int>(), row_sorted.data_ptr<int>(), rsrc_p,           \
-      e.data_ptr<float>(), L_new.data_ptr<float>(),                          \
-      want_lgrad ? lgrad.data_ptr<float>() : nullptr,                        \
-      rgrad.data_ptr<float>(), sqerr.data_ptr<float>(), (int)n, m, k,        \
-      2.f * (float)lam, (float)max_val)
   // ring depth 4 with dots reduced in pairs: measured best of D = 2, 4, 8 on
   // MI355X at the bench shape (profiles/r03_nmf_step.md)
-  if (vec && !wide) NMF_STEP_LAUNCH(32, 4, 2, true);
-  else if (vec) NMF_STEP_LAUNCH(64, 4, 2, true);
-  else if (!wide) NMF_STEP_LAUNCH(32, 4, 2, false);
-  else NMF_STEP_LAUNCH(64, 4, 2, false);
-#undef NMF_STEP_LAUNCH
+  dispatch_pow2<32, 64>(__func__, "lanes per row", wide ? 64 : 32, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    dispatch_bool(vec, [&](auto v) {
+      constexpr bool VEC = decltype(v)::value;
+      constexpr int threads = 256, per = threads / G;
+      float* lg = want_lgrad ? lgrad.data_ptr<float>() : nullptr;
+      const float lam2 = 2.f * (float)lam;
+      if (n > 0)
+        hipLaunchKernelGGL((nmf_step_a_kernel<G, 4, 2, VEC>),
+                           dim3((n + per - 1) / per), dim3(threads), 0,
+                           current_stream(), Lp, Rp, row_ptr.data_ptr<int>(),
+                           col.data_ptr<int>(), vals.data_ptr<float>(),
+                           step.data_ptr<float>(), e.data_ptr<float>(),
+                           L_new.data_ptr<float>(), lg,
+                           sqerr.data_ptr<float>(), (int)n, k, lam2,
+                           (float)max_val);
+      if (m > 0)
+        hipLaunchKernelGGL((nmf_step_b_kernel<G, 4, VEC>),
+                           dim3((m + per - 1) / per), dim3(threads), 0,
+                           current_stream(), Lp, Rp, e.data_ptr<float>(),
+                           perm.data_ptr<int>(), seg_ptr.data_ptr<int>(),
+                           row_sorted.data_ptr<int>(), rsrc_p,
+                           rgrad.data_ptr<float>(), m, k, lam2);
+    });
+  });
   if (want_lgrad) return {L_new, rgrad, sqerr, lgrad};
   return {L_new, rgrad, sqerr};
 }

@@ -131,7 +131,8 @@ torch::Tensor os_shard_alloc(int64_t rows, int64_t k, int64_t dtype_i32) {
 }
 
 torch::Tensor os_ipc_handle(torch::Tensor shard) {
-  CHECK_IN(shard);
+  TORCH_CHECK(shard.is_cuda() && shard.is_contiguous(),
+              "os_ipc_handle: shard must be contiguous on device");
   hipIpcMemHandle_t h;
   TORCH_CHECK(hipIpcGetMemHandle(&h, shard.data_ptr()) == hipSuccess,
               "hipIpcGetMemHandle failed (needs dmabuf IPC: "
@@ -158,7 +159,11 @@ void os_ipc_close(int64_t ptr) {
 
 torch::Tensor os_gather(int64_t ptr, torch::Tensor idx, int64_t k,
                         int64_t dtype_i32) {
-  CHECK_IN(idx);
+  check_tensor(__func__, idx, "idx", torch::kInt64, {-1});
+  TORCH_CHECK(ptr != 0 && k >= 1, __func__,
+              ": needs a mapped shard and k >= 1");
+  check_below_2_31(__func__, {{"n", idx.numel()}, {"k", k}});
+  check_on_device(__func__, {idx});
   const int n = idx.numel();
   auto out = torch::empty(
       {(int64_t)n, k},
@@ -180,11 +185,17 @@ torch::Tensor os_gather(int64_t ptr, torch::Tensor idx, int64_t k,
 }
 
 void os_scatter_add(int64_t ptr, torch::Tensor idx, torch::Tensor delta) {
-  CHECK_IN(idx); CHECK_IN(delta);
+  check_tensor(__func__, idx, "idx", torch::kInt64, {-1});
+  const bool i32 = delta.scalar_type() == torch::kInt32;
+  check_tensor(__func__, delta, "delta", i32 ? torch::kInt32 : torch::kFloat32,
+               {idx.numel(), -1});
+  TORCH_CHECK(ptr != 0, __func__, ": needs a mapped shard");
+  check_below_2_31(__func__, {{"n", idx.numel()}, {"k", delta.size(1)}});
+  check_on_device(__func__, {idx, delta});
   const int n = idx.numel();
   if (n == 0) return;
   const int k = delta.size(1);
-  if (delta.scalar_type() == torch::kInt32)
+  if (i32)
     hipLaunchKernelGGL(scatter_add_rows_i32_kernel, grid_for((int64_t)n * k),
                        dim3(GATHER_THREADS), 0, current_stream(),
                        (int*)(uintptr_t)ptr, idx.data_ptr<int64_t>(),

@@ -141,39 +141,65 @@ int64_t os_ring_bytes(int64_t W, int64_t cap, int64_t vd) {
   return 2 * W * 8 + W * cap * 4 + W * cap * 4 + W * cap * vd * 4;
 }
 
+// The ring a peer mapped at `base`: W writers, cap slots of vd floats each.
+static void check_ring(const char* op, int64_t base, int64_t W, int64_t cap,
+                       int64_t vd, int64_t writer) {
+  TORCH_CHECK(base != 0 && writer >= 0 && writer < W, op,
+              ": needs a mapped ring and a writer in [0, W = ", W, ")");
+  TORCH_CHECK(W >= 1 && cap >= 1 && vd >= 1, op, ": W, cap, vd >= 1");
+  check_below_2_31(op, {{"W", W}, {"vd", vd}});
+}
+
+static unsigned long long* check_seq(const char* op, const torch::Tensor& t,
+                                     const char* name) {
+  check_tensor(op, t, name, torch::kInt64, {-1});
+  TORCH_CHECK(t.numel() >= 1, op, ": ", name, " must hold a sequence number");
+  return (unsigned long long*)t.data_ptr<int64_t>();
+}
+
 void os_ring_reserve(int64_t base, int64_t W, int64_t cap, int64_t vd,
                      int64_t writer, int64_t n, torch::Tensor scratch) {
+  check_ring(__func__, base, W, cap, vd, writer);
+  TORCH_CHECK(n >= 0, __func__, ": n >= 0");
+  auto* sp = check_seq(__func__, scratch, "scratch");
+  check_on_device(__func__, {scratch});
   hipLaunchKernelGGL(ring_reserve_kernel, dim3(1), dim3(1), 0,
                      current_stream(), (void*)(uintptr_t)base, (int)W, cap,
-                     (int)vd, (int)writer, n,
-                     (unsigned long long*)scratch.data_ptr());
+                     (int)vd, (int)writer, n, sp);
 }
 
 void os_ring_read_head(int64_t base, int64_t W, int64_t cap, int64_t vd,
                        int64_t writer, torch::Tensor scratch) {
+  check_ring(__func__, base, W, cap, vd, writer);
+  auto* sp = check_seq(__func__, scratch, "scratch");
+  check_on_device(__func__, {scratch});
   hipLaunchKernelGGL(ring_read_head_kernel, dim3(1), dim3(1), 0,
                      current_stream(), (void*)(uintptr_t)base, (int)W, cap,
-                     (int)vd, (int)writer,
-                     (unsigned long long*)scratch.data_ptr());
+                     (int)vd, (int)writer, sp);
 }
 
 void os_ring_push(int64_t base, int64_t W, int64_t cap, int64_t vd,
                   int64_t writer, torch::Tensor seq_base,
                   torch::Tensor keys, torch::Tensor deltas) {
-  CHECK_IN(keys); CHECK_IN(deltas);
+  check_ring(__func__, base, W, cap, vd, writer);
+  const auto* sp = check_seq(__func__, seq_base, "seq_base");
+  check_tensor(__func__, keys, "keys", torch::kInt64, {-1});
   const long n = keys.numel();
+  check_tensor(__func__, deltas, "deltas", torch::kFloat32, {n, vd});
+  check_below_2_31(__func__, {{"n", n}});
+  check_on_device(__func__, {seq_base, keys, deltas});
   if (n == 0) return;
-  TORCH_CHECK(deltas.size(0) == n && deltas.size(1) == vd);
   hipLaunchKernelGGL(ring_push_kernel, dim3((unsigned)n), dim3(64), 0,
                      current_stream(), (void*)(uintptr_t)base, (int)W, cap,
-                     (int)vd, (int)writer,
-                     (const unsigned long long*)seq_base.data_ptr(),
-                     keys.data_ptr<int64_t>(), deltas.data_ptr<float>(), n);
+                     (int)vd, (int)writer, sp, keys.data_ptr<int64_t>(),
+                     deltas.data_ptr<float>(), n);
 }
 
 std::vector<torch::Tensor> os_ring_drain(int64_t base, int64_t W,
                                          int64_t cap, int64_t vd,
                                          int64_t max_per) {
+  check_ring(__func__, base, W, cap, vd, 0);
+  TORCH_CHECK(max_per >= 1, __func__, ": max_per >= 1");
   auto dev = torch::TensorOptions().device(torch::kCUDA);
   auto keys = torch::empty({W * max_per}, dev.dtype(torch::kInt64));
   auto deltas = torch::empty({W * max_per, vd}, dev.dtype(torch::kFloat32));

@@ -72,24 +72,6 @@ __global__ __launch_bounds__(kBlock) void pregel_pull_kernel(
   }
 }
 
-template <int G>
-void launch(bool is_min, bool addw, dim3 grid, hipStream_t st,
-            const int64_t* in_ptr, const int* in_src, const float* in_w,
-            float w_const, const float* vert_msg, const uint8_t* mask,
-            float* out, uint8_t* flag, int64_t R, int64_t n_local,
-            int64_t n_edges) {
-#define PULL(MINV, ADDV)                                                     \
-  hipLaunchKernelGGL((pregel_pull_kernel<G, MINV, ADDV>), grid, dim3(kBlock), \
-                     0, st, in_ptr, in_src, in_w, w_const, vert_msg, mask,   \
-                     out, flag, R, n_local, n_edges)
-  if (is_min) {
-    if (addw) PULL(true, true); else PULL(true, false);
-  } else {
-    if (addw) PULL(false, true); else PULL(false, false);
-  }
-#undef PULL
-}
-
 }  // namespace
 
 // combiner: 0 = add, 1 = min. group: lanes per row, a power of two in 1..64.
@@ -98,55 +80,40 @@ std::vector<torch::Tensor> pregel_pull(
     c10::optional<torch::Tensor> in_w, double w_const, torch::Tensor vert_msg,
     c10::optional<torch::Tensor> send_mask, int64_t combiner, bool add_weight,
     int64_t group) {
-  CHECK_IN(in_ptr); CHECK_IN(in_src); CHECK_IN(vert_msg);
-  TORCH_CHECK(in_ptr.dtype() == torch::kInt64 && in_ptr.dim() == 1 &&
-              in_ptr.numel() >= 1, "in_ptr must be int64 [R+1]");
-  TORCH_CHECK(in_src.dtype() == torch::kInt32 && in_src.dim() == 1,
-              "in_src must be int32 [Ein]");
-  TORCH_CHECK(vert_msg.dtype() == torch::kFloat32 && vert_msg.dim() == 1,
-              "vert_msg must be float32 [n_local] (msg_dim == 1 only)");
-  TORCH_CHECK(combiner == 0 || combiner == 1, "combiner: 0 add, 1 min");
-  TORCH_CHECK(group >= 1 && group <= 64 && (group & (group - 1)) == 0,
-              "group must be a power of two in 1..64");
+  check_tensor(__func__, in_ptr, "in_ptr", torch::kInt64, {-1});
+  check_tensor(__func__, in_src, "in_src", torch::kInt32, {-1});
+  check_tensor(__func__, vert_msg, "vert_msg", torch::kFloat32, {-1});  // 1-D
   const int64_t R = in_ptr.numel() - 1;
   const int64_t n_edges = in_src.numel();
   const int64_t n_local = vert_msg.numel();
-  TORCH_CHECK(n_local < (int64_t)1 << 31 && n_edges < (int64_t)1 << 31,
-              "pregel_pull: n_local and Ein must be below 2^31");
-  const float* wp = nullptr;
-  if (in_w.has_value()) {
-    CHECK_IN(*in_w);
-    TORCH_CHECK(in_w->dtype() == torch::kFloat32 &&
-                in_w->numel() == n_edges, "in_w must be float32 [Ein]");
-    wp = in_w->data_ptr<float>();
-  }
-  const uint8_t* mp = nullptr;
-  if (send_mask.has_value()) {
-    CHECK_IN(*send_mask);
-    TORCH_CHECK(send_mask->dtype() == torch::kUInt8 &&
-                send_mask->numel() == n_local,
-                "send_mask must be uint8 [n_local]");
-    mp = send_mask->data_ptr<uint8_t>();
-  }
+  const float* wp = check_tensor<float>(__func__, in_w, "in_w", {n_edges});
+  const uint8_t* mp =
+      check_tensor<uint8_t>(__func__, send_mask, "send_mask", {n_local});
+  TORCH_CHECK(combiner == 0 || combiner == 1, __func__,
+              ": combiner: 0 add, 1 min");
+  check_pow2<1, 64>(__func__, "group", group);
+  check_below_2_31(__func__,
+                   {{"R", R}, {"n_local", n_local}, {"Ein", n_edges}});
+  check_on_device(__func__, {in_ptr, in_src, vert_msg, in_w, send_mask});
   auto out = torch::empty({R}, vert_msg.options());
   auto flag = torch::empty({R}, vert_msg.options().dtype(torch::kUInt8));
   if (R == 0) return {out, flag};
   const int64_t rows_per_block = kBlock / group;
-  const int64_t want = (R + rows_per_block - 1) / rows_per_block;
-  // memory-bound: cap the grid and let the groups stride over the rest
-  dim3 grid((unsigned)std::min<int64_t>(want, 256 * 8 * 4));
+  const dim3 grid = strided_grid((R + rows_per_block - 1) / rows_per_block);
   hipStream_t st = current_stream();
-#define GO(GV)                                                               \
-  case GV:                                                                   \
-    launch<GV>(combiner == 1, add_weight, grid, st,                          \
-               in_ptr.data_ptr<int64_t>(), in_src.data_ptr<int>(), wp,       \
-               (float)w_const, vert_msg.data_ptr<float>(), mp,               \
-               out.data_ptr<float>(), flag.data_ptr<uint8_t>(), R, n_local,  \
-               n_edges);                                                     \
-    break
-  switch (group) {
-    GO(1); GO(2); GO(4); GO(8); GO(16); GO(32); GO(64);
-  }
-#undef GO
+  dispatch_pow2<1, 64>(__func__, "group", group, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    dispatch_bool(combiner == 1, [&](auto is_min) {
+      dispatch_bool(add_weight, [&](auto addw) {
+        hipLaunchKernelGGL(
+            (pregel_pull_kernel<G, decltype(is_min)::value,
+                                decltype(addw)::value>),
+            grid, dim3(kBlock), 0, st, in_ptr.data_ptr<int64_t>(),
+            in_src.data_ptr<int>(), wp, (float)w_const,
+            vert_msg.data_ptr<float>(), mp, out.data_ptr<float>(),
+            flag.data_ptr<uint8_t>(), R, n_local, n_edges);
+      });
+    });
+  });
   return {out, flag};
 }

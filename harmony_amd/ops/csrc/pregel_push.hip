@@ -132,40 +132,22 @@ std::vector<torch::Tensor> pregel_push(
     torch::Tensor vert_msg, torch::Tensor frontier,
     c10::optional<torch::Tensor> send_mask, int64_t num_rows,
     bool add_weight, int64_t edges_hint) {
-  CHECK_IN(out_ptr); CHECK_IN(out_row); CHECK_IN(vert_msg);
-  CHECK_IN(frontier);
-  TORCH_CHECK(out_ptr.dtype() == torch::kInt64 && out_ptr.dim() == 1 &&
-              out_ptr.numel() >= 1, "out_ptr must be int64 [n_local+1]");
-  TORCH_CHECK(out_row.dtype() == torch::kInt32 && out_row.dim() == 1,
-              "out_row must be int32 [E]");
-  TORCH_CHECK(vert_msg.dtype() == torch::kFloat32 && vert_msg.dim() == 1,
-              "vert_msg must be float32 [n_local] (msg_dim == 1 only)");
-  TORCH_CHECK(frontier.dtype() == torch::kInt32 && frontier.dim() == 1,
-              "frontier must be int32 [nf]");
+  check_tensor(__func__, out_ptr, "out_ptr", torch::kInt64, {-1});
+  check_tensor(__func__, out_row, "out_row", torch::kInt32, {-1});
   const int64_t n_local = out_ptr.numel() - 1;
   const int64_t n_edges = out_row.numel();
+  // msg_dim == 1 only
+  check_tensor(__func__, vert_msg, "vert_msg", torch::kFloat32, {n_local});
+  check_tensor(__func__, frontier, "frontier", torch::kInt32, {-1});
   const int64_t nf = frontier.numel();
   const int64_t R = num_rows;
-  TORCH_CHECK(vert_msg.numel() == n_local,
-              "vert_msg must have one entry per local vertex");
-  TORCH_CHECK(R >= 0 && R < (int64_t)1 << 31 &&
-              n_local < (int64_t)1 << 31 && n_edges < (int64_t)1 << 31,
-              "pregel_push: num_rows, n_local and E must be below 2^31");
-  const float* wp = nullptr;
-  if (out_w.has_value()) {
-    CHECK_IN(*out_w);
-    TORCH_CHECK(out_w->dtype() == torch::kFloat32 &&
-                out_w->numel() == n_edges, "out_w must be float32 [E]");
-    wp = out_w->data_ptr<float>();
-  }
-  const uint8_t* mp = nullptr;
-  if (send_mask.has_value()) {
-    CHECK_IN(*send_mask);
-    TORCH_CHECK(send_mask->dtype() == torch::kUInt8 &&
-                send_mask->numel() == n_local,
-                "send_mask must be uint8 [n_local]");
-    mp = send_mask->data_ptr<uint8_t>();
-  }
+  const float* wp = check_tensor<float>(__func__, out_w, "out_w", {n_edges});
+  const uint8_t* mp =
+      check_tensor<uint8_t>(__func__, send_mask, "send_mask", {n_local});
+  check_below_2_31(__func__,
+                   {{"num_rows", R}, {"n_local", n_local}, {"E", n_edges}});
+  check_on_device(__func__, {out_ptr, out_row, vert_msg, frontier, out_w,
+                  send_mask});
   if (nf == 0 || R == 0 || n_edges == 0) {
     return {torch::full({R}, std::numeric_limits<float>::infinity(),
                         vert_msg.options()),
@@ -189,15 +171,15 @@ std::vector<torch::Tensor> pregel_push(
   if (edges_hint >= 0) want = (edges_hint + kBlock - 1) / kBlock;
   const int64_t grid =
       std::max<int64_t>(1, std::min<int64_t>(want, kMaxGrid));
-#define PUSH(ADDV)                                                           \
-  hipLaunchKernelGGL((pregel_push_kernel<ADDV>), dim3((unsigned)grid),       \
-                     dim3(kBlock), 0, st, out_ptr.data_ptr<int64_t>(),       \
-                     out_row.data_ptr<int>(), wp, (float)w_const,            \
-                     vert_msg.data_ptr<float>(), frontier.data_ptr<int>(),   \
-                     fptr.data_ptr<int64_t>(),                               \
-                     reinterpret_cast<int*>(out.data_ptr<float>()),          \
-                     flag.data_ptr<uint8_t>(), nf, R, n_local, n_edges)
-  if (add_weight) PUSH(true); else PUSH(false);
-#undef PUSH
+  dispatch_bool(add_weight, [&](auto addw) {
+    hipLaunchKernelGGL(
+        (pregel_push_kernel<decltype(addw)::value>), dim3((unsigned)grid),
+        dim3(kBlock), 0, st, out_ptr.data_ptr<int64_t>(),
+        out_row.data_ptr<int>(), wp, (float)w_const,
+        vert_msg.data_ptr<float>(), frontier.data_ptr<int>(),
+        fptr.data_ptr<int64_t>(),
+        reinterpret_cast<int*>(out.data_ptr<float>()),
+        flag.data_ptr<uint8_t>(), nf, R, n_local, n_edges);
+  });
   return {out, flag};
 }

@@ -82,60 +82,67 @@ static void launch_scatter_apply(torch::Tensor& shard, torch::Tensor& rows,
                                  int mode, float step, float maxval) {
   T* sp = shard.data_ptr<T>();
   const T* dp = deltas.data_ptr<T>();
-  const bool vec = vd % 4 == 0 &&
-                   ((reinterpret_cast<uintptr_t>(sp) |
-                     reinterpret_cast<uintptr_t>(dp)) & 15) == 0;
+  const bool vec = vd % 4 == 0 && aligned16(sp) && aligned16(dp);
   const int units = vec ? vd / 4 : vd;   // accesses per row
   int log2g = 0;
   while (log2g < 6 && (1 << log2g) < units) ++log2g;
   const int64_t threads = n << log2g;
   dim3 blk(256), grid((unsigned)((threads + 255) / 256));
-  if (vec)
-    hipLaunchKernelGGL((scatter_apply_kernel<T, true>), grid, blk, 0,
-                       current_stream(), sp, rows.data_ptr<int64_t>(), dp, n,
-                       vd, log2g, mode, step, maxval);
-  else
-    hipLaunchKernelGGL((scatter_apply_kernel<T, false>), grid, blk, 0,
-                       current_stream(), sp, rows.data_ptr<int64_t>(), dp, n,
-                       vd, log2g, mode, step, maxval);
+  dispatch_bool(vec, [&](auto v) {
+    hipLaunchKernelGGL((scatter_apply_kernel<T, decltype(v)::value>), grid,
+                       blk, 0, current_stream(), sp, rows.data_ptr<int64_t>(),
+                       dp, n, vd, log2g, mode, step, maxval);
+  });
+}
+
+static at::ScalarType apply_dtype(const char* op, const torch::Tensor& shard) {
+  const auto dt = shard.scalar_type();
+  TORCH_CHECK(dt == torch::kFloat32 || dt == torch::kInt32, op,
+              ": shard must be float32 or int32, got ", dt);
+  return dt;
 }
 
 void scatter_apply(torch::Tensor shard, torch::Tensor rows,
                    torch::Tensor deltas, int64_t mode, double step,
                    double maxval) {
-  CHECK_IN(shard); CHECK_IN(rows); CHECK_IN(deltas);
+  const auto dt = apply_dtype(__func__, shard);
+  check_tensor(__func__, shard, "shard", dt, {-1, -1});
+  check_tensor(__func__, rows, "rows", torch::kInt64, {-1});
   const int64_t n = rows.size(0);
   const int vd = shard.size(1);
+  check_tensor(__func__, deltas, "deltas", dt, {n, shard.size(1)});
+  check_below_2_31(__func__, {{"row width", shard.size(1)}});
+  check_on_device(__func__, {shard, rows, deltas});
   if (n == 0 || vd == 0) return;
-  if (shard.dtype() == torch::kFloat32) {
+  if (dt == torch::kFloat32) {
     launch_scatter_apply<float>(shard, rows, deltas, n, vd, (int)mode,
                                 (float)step, (float)maxval);
-  } else if (shard.dtype() == torch::kInt32) {
+  } else {
     launch_scatter_apply<int>(shard, rows, deltas, n, vd, (int)mode,
                               (float)step, (float)maxval);
-  } else {
-    TORCH_CHECK(false, "scatter_apply: unsupported dtype");
   }
 }
 
 void dense_apply(torch::Tensor shard, torch::Tensor delta, int64_t mode,
                  double step, double maxval) {
-  CHECK_IN(shard); CHECK_IN(delta);
+  const auto dt = apply_dtype(__func__, shard);
+  check_tensor(__func__, shard, "shard", dt, shard.sizes());
+  check_tensor(__func__, delta, "delta", dt, delta.sizes());
   const int64_t total = shard.numel();
-  TORCH_CHECK(delta.numel() == total, "size mismatch");
+  TORCH_CHECK(delta.numel() == total, __func__, ": delta must hold ", total,
+              " elements like shard, got ", delta.numel());
+  check_on_device(__func__, {shard, delta});
   if (total == 0) return;
   dim3 blk(256), grid((unsigned)((total + 255) / 256));
-  if (shard.dtype() == torch::kFloat32) {
+  if (dt == torch::kFloat32) {
     hipLaunchKernelGGL(dense_apply_kernel<float>, grid, blk, 0,
                        current_stream(), shard.data_ptr<float>(),
                        delta.data_ptr<float>(), total, (int)mode, (float)step,
                        (float)maxval);
-  } else if (shard.dtype() == torch::kInt32) {
+  } else {
     hipLaunchKernelGGL(dense_apply_kernel<int>, grid, blk, 0,
                        current_stream(), shard.data_ptr<int>(),
                        delta.data_ptr<int>(), total, (int)mode, (float)step,
                        (float)maxval);
-  } else {
-    TORCH_CHECK(false, "dense_apply: unsupported dtype");
   }
 }
