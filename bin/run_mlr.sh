@@ -5,5 +5,7 @@
 # -test_data_path <file> (with or without file://): a held-out file in the
 # -input format, read whole by every rank before training; the summary then
 # holds test_cross_entropy, test_accuracy and test_examples.
+# -data_dtype bfloat16 (default float32): dense blocks, training and held-out,
+# are kept as bf16 and the step runs the K4-BF16 kernels.
 cd "$(dirname "$0")/.."
 exec python -m harmony_amd.standalone -app mlr "$@"

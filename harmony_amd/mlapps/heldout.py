@@ -46,6 +46,14 @@ def load_rows(path: str, num_features: int, sparse: bool):
     return dl.parse_libsvm_split(path, 0, 1, num_features)
 
 
+def stored(X: torch.Tensor, a: dict) -> torch.Tensor:
+    """A dense block's X as the app keeps it: rounded to bf16 (to nearest
+    even) under the MLR app arg data_dtype=bfloat16, else as it is."""
+    if a.get("data_dtype") == "bfloat16":
+        return X.to(torch.bfloat16)
+    return X
+
+
 def row_blocks(a: dict, device: torch.device, label_dtype=None) -> List:
     """The test rows of app args `a` (an app's defaults(): num_features,
     batch_size, sparse) in blocks of at most batch_size rows, (X, y) or
@@ -71,7 +79,7 @@ def row_blocks(a: dict, device: torch.device, label_dtype=None) -> List:
     if label_dtype is not None:
         y = y.to(label_dtype)
     for lo in range(0, y.shape[0], size):
-        blocks.append((X[lo:lo + size].to(device),
+        blocks.append((stored(X[lo:lo + size], a).to(device),
                        y[lo:lo + size].to(device)))
     return blocks
 

@@ -22,7 +22,14 @@ the synthetic sparse generator; test_data_path (mlapps/heldout.py; reference
 TestDataProvider): a held-out file read whole by every rank in build(), cut
 into blocks of at most batch_size rows; evaluate_test() reports
 test_cross_entropy, test_accuracy and test_examples for the final model and
-for every offline checkpoint.
+for every offline checkpoint; data_dtype (float32, the default, or bfloat16):
+with bfloat16 every dense block's X, training and held-out, synthetic or
+from -input, is rounded to bf16 once at load time (round to nearest even)
+and kept so, half the bytes per resident batch and per pass over it. Labels,
+the model table, the pulled W, the gradient and the push stay float32. The
+step then runs the K4-BF16 kernels (ops/csrc/mlr_bf16.hip): bf16 MFMA with W
+and P split into three bf16 terms each, so nothing beyond the data itself is
+rounded to bf16. Not available with sparse=true.
 """
 
 from __future__ import annotations
@@ -45,12 +52,22 @@ MODEL_TABLE = "mlr_model"
 def defaults(job: JobConfig) -> dict:
     a = dict(num_classes=10, num_features=1024, num_parts_per_class=8,
              batch_size=4096, step_size=0.01, lam=1e-4, dtype="float32",
-             decay_rate=0.9, decay_period=5, sparse="false", nnz_per_row=32)
+             decay_rate=0.9, decay_period=5, sparse="false", nnz_per_row=32,
+             data_dtype="float32")
     a.update(job.app_args)
     return a
 
 
 _is_sparse = is_sparse
+
+
+def _check_data_dtype(a: dict) -> None:
+    if a["data_dtype"] not in ("float32", "bfloat16"):
+        raise ValueError(f"data_dtype must be float32 or bfloat16, got "
+                         f"{a['data_dtype']!r}")
+    if a["data_dtype"] == "bfloat16" and _is_sparse(a):
+        raise ValueError("data_dtype=bfloat16 needs dense batches "
+                         "(sparse=true keeps float32 values)")
 
 
 def model_table_cfg(job: JobConfig, world_size: int) -> TableConfig:
@@ -89,7 +106,8 @@ def make_batches(job: JobConfig, rank: int, device: torch.device,
         n_blocks = max(1, job.num_worker_blocks or job.num_mini_batches)
         xs = torch.chunk(X, n_blocks)
         ys = torch.chunk(y.long(), n_blocks)
-        return [(x.to(device), yy.to(device)) for x, yy in zip(xs, ys)]
+        return [(heldout.stored(x, a).to(device), yy.to(device))
+                for x, yy in zip(xs, ys)]
     C, F, B = a["num_classes"], a["num_features"], a["batch_size"]
     from harmony_amd.utils import stable_seed
 
@@ -100,7 +118,7 @@ def make_batches(job: JobConfig, rank: int, device: torch.device,
     for _ in range(n_blocks):
         y = torch.randint(0, C, (B,), generator=g)
         x = centers[y] + torch.randn(B, F, generator=g)
-        blocks.append((x.to(device), y.to(device)))
+        blocks.append((heldout.stored(x, a).to(device), y.to(device)))
     return blocks
 
 
@@ -239,7 +257,16 @@ class MLRTrainer(Trainer):
             if rb and (x.shape[0] % rb or rb % 64):
                 rb = 0
 
-            if use_mfma:
+            if x.dtype == torch.bfloat16:
+                # data_dtype=bfloat16: the K4-BF16 step (ops/csrc/
+                # mlr_bf16.hip; A/B scripts/mlr_bf16_ab.py)
+                def body(x=x, y=y, W=W):
+                    g, loss, correct = ops.mlr_step_mfma(
+                        x, W, y, Wt_buf=self._wt_buf())
+                    self.grad_raw = g / x.shape[0] + self.a["lam"] * W
+                    self._loss_sum += loss
+                    self._correct += correct
+            elif use_mfma:
                 # fused fwd+softmax+grad on f32 MFMA, L3 row-blocked
                 # (K4-MFMA, ops/csrc/mlr_mfma.hip; A/B scripts/mlr_mfma_ab.py)
                 def body(x=x, y=y, W=W, rb=rb):
@@ -315,6 +342,7 @@ class MLRTrainer(Trainer):
 
 
 def build(job: JobConfig, ctx, cp):
+    _check_data_dtype(defaults(job))
     # before anything else: a missing test file fails the job at once
     test_blocks = heldout.row_blocks(defaults(job), ctx.device,
                                      label_dtype=torch.int64)

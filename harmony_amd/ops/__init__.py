@@ -13,6 +13,7 @@ Kernel inventory (reference hot loops):
   K3  (fused in push)     NMFETModelUpdateFunction.java:48-52
   K4  mlr softmax+grad    MLRTrainer.java:374-398,475-489
   K4s mlr_sparse_fwd/grad MLRTrainer.java:374-398 over SparseVector rows
+  K4-BF16 mlr_step_mfma   K4-MFMA's step on bfloat16 X (three-term bf16 split)
   K7  lda_gibbs           SparseLDASampler.java:141-274
   K7e lda_foldin          held-out document completion (TestDataProvider)
   K9  scatter-apply       LDAETModelUpdateFunction.java:43-64
@@ -96,13 +97,102 @@ def mlr_forward(X: torch.Tensor, W: torch.Tensor, labels: torch.Tensor
     # kernel (0.685 ms) only looked competitive against concurrency-inflated
     # profile times. GEMM + the small fused softmax kernel is the fast path;
     # mlr_fwd stays available for C<=16 regression testing.
+    if X.dtype == torch.bfloat16:
+        return softmax_grad_ce(_bf16_logits(X, W), labels)
     return softmax_grad_ce(X @ W.t(), labels)
 
 
 def mlr_grad_gemm(P: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
     """grad = P^T @ X. rocBLAS measured 0.212 ms vs the custom B-tile kernel's
     0.520 ms (scripts/mlr_ab.py) — Tensile's split-K wins this shape."""
+    if X.dtype == torch.bfloat16:
+        return _bf16_grad(P, X)
     return P.t() @ X
+
+
+# bf16 training data (MLR app arg data_dtype=bfloat16; K4-BF16,
+# ops/csrc/mlr_bf16.hip). X alone is bf16; W, P, the gradient, loss and
+# counts stay float32. CPU tensors and HARMONY_FORCE_TORCH_OPS=1 compute with
+# X.float() by the float32 tensor ops; on the GPU, shapes the kernels do not
+# take go through the same tensor ops in row chunks, so that no [B, F]
+# float32 copy of the batch is ever made.
+_BF16_CHUNK = 4096
+
+
+def mlr_bf16_ok(X: torch.Tensor, C: int) -> bool:
+    """Shapes the bf16 MFMA kernels take (see mlr_bf16.hip)."""
+    return (X.dtype == torch.bfloat16 and X.dim() == 2 and X.shape[0] >= 1
+            and 1 <= C <= 16 and X.shape[1] >= 32 and X.shape[1] % 32 == 0)
+
+
+def mlr_bf16_splits(B: int, F: int) -> Tuple[int, int]:
+    """(splitf, splitb) of the bf16 kernels: a pure function of the shape
+    aiming at about 512 workgroups per launch (256 rows per forward
+    workgroup, 128 features per gradient workgroup)."""
+    splitf = _pow2_div(max(1, 512 // -(-B // 256)), F // 32)
+    splitb = max(1, min(512 // -(-F // 128), -(-B // 64)))
+    return splitf, splitb
+
+
+def _bf16_wt(W: torch.Tensor, Wt_buf: Optional[torch.Tensor]) -> torch.Tensor:
+    C, F = W.shape
+    if Wt_buf is None:
+        Wt_buf = torch.zeros((F, 16), dtype=torch.float32, device=W.device)
+    Wt_buf[:, :C] = W.t()
+    return Wt_buf
+
+
+def _bf16_chunks(X: torch.Tensor):
+    for lo in range(0, X.shape[0], _BF16_CHUNK):
+        yield lo, X[lo:lo + _BF16_CHUNK].float()
+
+
+def _bf16_logits(X: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
+    C, F = W.shape
+    if not _use_hip(X):
+        return X.float() @ W.t()
+    B = X.shape[0]
+    if not mlr_bf16_ok(X, C):
+        if B <= _BF16_CHUNK:
+            return X.float() @ W.t()
+        return torch.cat([xf @ W.t() for _lo, xf in _bf16_chunks(X)])
+    P = torch.empty((B, 16), dtype=torch.float32, device=X.device)
+    _hip.mlr_fwd_mfma_part(X.contiguous(), _bf16_wt(W, None), P, 0, B,
+                           mlr_bf16_splits(B, F)[0])
+    return P[:, :C]
+
+
+def _bf16_grad(P: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+    B, C = P.shape
+    F = X.shape[1]
+    if not _use_hip(X):
+        return P.t() @ X.float()
+    if not mlr_bf16_ok(X, C):
+        g = torch.zeros((C, F), dtype=torch.float32, device=X.device)
+        for lo, xf in _bf16_chunks(X):
+            g += P[lo:lo + _BF16_CHUNK].t() @ xf
+        return g
+    P16 = torch.zeros((B, 16), dtype=torch.float32, device=X.device)
+    P16[:, :C] = P
+    gradT = torch.zeros((16, F), dtype=torch.float32, device=X.device)
+    _hip.mlr_grad_mfma_part(P16, X.contiguous(), gradT, 0, B,
+                            mlr_bf16_splits(B, F)[1])
+    return gradT[:C]
+
+
+def _bf16_step(X: torch.Tensor, W: torch.Tensor, labels: torch.Tensor,
+               row_block: int, splitf: Optional[int], splitb: Optional[int],
+               Wt_buf: Optional[torch.Tensor]):
+    C, F = W.shape
+    B = X.shape[0]
+    if not _use_hip(X) or not mlr_bf16_ok(X, C):
+        p, loss, correct = mlr_forward(X, W, labels)
+        return mlr_grad_gemm(p, X), loss, correct
+    sf, sb = mlr_bf16_splits(B, F)
+    gradT, loss, correct = _hip.mlr_step_mfma(
+        X.contiguous(), _bf16_wt(W, Wt_buf), labels.contiguous(), row_block,
+        C, sf if splitf is None else splitf, sb if splitb is None else splitb)
+    return gradT[:C], loss[0], correct[0].to(torch.int64)
 
 
 def mlr_step_ok(X: torch.Tensor, C: int) -> bool:
@@ -134,8 +224,16 @@ def mlr_step_mfma(X: torch.Tensor, W: torch.Tensor, labels: torch.Tensor,
     numerics (a k-ordered fmaf chain).
 
     Replaces reference MLRTrainer.java:374-398 + :475-489 + the rocBLAS
-    GEMM pair (measured A/B: scripts/mlr_mfma_ab.py)."""
+    GEMM pair (measured A/B: scripts/mlr_mfma_ab.py).
+
+    A bfloat16 X takes the K4-BF16 kernels (ops/csrc/mlr_bf16.hip,
+    v_mfma_f32_16x16x32_bf16 with W and P split into three bf16 terms, so
+    the products stay exact; no atomics, bit-identical from run to run)
+    when mlr_bf16_ok(X, C); row_block must then be 0 and Wt_buf is float32
+    [F, 16] as for float32 X."""
     C, F = W.shape
+    if X.dtype == torch.bfloat16:
+        return _bf16_step(X, W, labels, row_block, splitf, splitb, Wt_buf)
     if not _use_hip(X):                # CPU oracle path
         p, loss, correct = mlr_forward(X, W, labels)
         return mlr_grad_gemm(p, X), loss, correct

@@ -204,8 +204,24 @@ static void check_window(const char* op, int64_t off, int64_t n, int64_t B) {
   check_below_2_31(op, {{"n", n}});
 }
 
+// bfloat16 X: the K4-BF16 kernels (mlr_bf16.hip), by dtype dispatch in the
+// three entries below; float32 X is untouched by it.
+void mlr_bf16_fwd_part(const char* op, torch::Tensor X, torch::Tensor Wt,
+                       torch::Tensor P, int64_t off, int64_t n,
+                       int64_t splitf);
+void mlr_bf16_grad_part(const char* op, torch::Tensor P, torch::Tensor X,
+                        torch::Tensor gradT, int64_t off, int64_t n,
+                        int64_t splitb);
+std::vector<torch::Tensor> mlr_bf16_step(const char* op, torch::Tensor X,
+                                         torch::Tensor Wt,
+                                         torch::Tensor labels,
+                                         int64_t row_block, int64_t C,
+                                         int64_t splitf, int64_t splitb);
+
 void mlr_fwd_mfma_part(torch::Tensor X, torch::Tensor Wt, torch::Tensor P,
                        int64_t off, int64_t n, int64_t splitf) {
+  if (X.scalar_type() == torch::kBFloat16)
+    return mlr_bf16_fwd_part(__func__, X, Wt, P, off, n, splitf);
   check_tensor(__func__, X, "X", torch::kFloat32, {-1, -1});
   const long B = X.size(0), F = X.size(1);
   check_tensor(__func__, Wt, "Wt", torch::kFloat32, {F, CPAD});
@@ -242,6 +258,8 @@ void mlr_softmax_part(torch::Tensor P, torch::Tensor labels,
 void mlr_grad_mfma_part(torch::Tensor P, torch::Tensor X,
                         torch::Tensor gradT, int64_t off, int64_t n,
                         int64_t splitb) {
+  if (X.scalar_type() == torch::kBFloat16)
+    return mlr_bf16_grad_part(__func__, P, X, gradT, off, n, splitb);
   check_tensor(__func__, X, "X", torch::kFloat32, {-1, -1});
   const long B = X.size(0), F = X.size(1);
   check_tensor(__func__, P, "P", torch::kFloat32, {B, CPAD});
@@ -265,6 +283,9 @@ std::vector<torch::Tensor> mlr_step_mfma(torch::Tensor X, torch::Tensor Wt,
                                          torch::Tensor labels,
                                          int64_t row_block, int64_t C,
                                          int64_t splitf, int64_t splitb) {
+  if (X.scalar_type() == torch::kBFloat16)
+    return mlr_bf16_step(__func__, X, Wt, labels, row_block, C, splitf,
+                         splitb);
   check_tensor(__func__, X, "X", torch::kFloat32, {-1, -1});
   const long B = X.size(0), F = X.size(1);
   check_tensor(__func__, Wt, "Wt", torch::kFloat32, {F, CPAD});
