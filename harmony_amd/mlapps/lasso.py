@@ -9,7 +9,9 @@ add (LassoETModelUpdateFunction.java:33).
 
 MI355X shape: the residual r = y - Xw is maintained incrementally so each
 coordinate step is two rocBLAS dot/axpy column ops on the device-resident
-batch; the full sweep stays on the GPU (F small relative to batch).
+batch; the full sweep stays on the GPU (F small relative to batch). A dense
+sweep is one launch for batches of up to 65536 rows (ops.lasso_cd: K11 up to
+16367 rows, K11L above); larger batches take the tensor-op loop.
 
 App args: num_features, num_parts, batch_size, lam, step_size(unused),
 noise, density; sparse (default false) and nnz_per_row (synthetic sparse

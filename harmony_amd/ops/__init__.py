@@ -22,6 +22,7 @@ Kernel inventory (reference hot loops):
   K10s gbt_hist_sparse    K10 over SparseVector samples (GBTETDataParser)
   K10p gbt_forest_predict GBTTrainer.java predictByTree over the whole forest
   K11 lasso_cd            LassoTrainer.java:164-190
+  K11L lasso_cd           K11 for 16368..65536 rows: residual in registers + LDS
   K11s lasso_cd_sparse    LassoTrainer.java:164-208 over SparseVector columns
   K12 loss reductions     NMFTrainer.java:414-456 etc.
   K13 pregel_pull         pregel MessageManager.addMessage + MessageCombiner
@@ -1332,18 +1333,26 @@ def gbt_forest_predict(bins, forest: torch.Tensor, depth: int,
         bins.key_bin.contiguous(), row_ptr)
 
 
+# rows the lasso_cd binding takes (K11, then K11L; the binding checks it)
+LASSO_CD_MAX_ROWS = 65536
+
+
 def lasso_cd(X: torch.Tensor, r: torch.Tensor, w: torch.Tensor,
              col_sq: torch.Tensor, lam_n: float
              ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """One full cyclic coordinate-descent sweep (K11): for each coordinate
-    the closed-form soft-threshold update (reference LassoTrainer.java:
+    """One full cyclic coordinate-descent sweep: for each coordinate the
+    closed-form soft-threshold update (reference LassoTrainer.java:
     164-190), residual maintained incrementally. Returns (w_new, r_new);
-    inputs are not mutated. GPU: single persistent workgroup, residual in
-    LDS (ops/csrc/lasso.hip); CPU: the tensor-op loop."""
+    inputs are not mutated. GPU: a single persistent workgroup behind one
+    binding. Up to 16367 rows K11 keeps the residual in 64 KiB of LDS
+    (ops/csrc/lasso.hip); from 16368 to LASSO_CD_MAX_ROWS rows K11L keeps
+    it in registers, and past 32768 rows the rest of it in LDS
+    (ops/csrc/lasso_large.hip). Larger batches, and CPU tensors, take the
+    tensor-op loop."""
     F = X.shape[1]
     w = w.clone()
     r = r.clone()
-    if _use_hip(X) and X.shape[0] + 17 <= 16384:
+    if _use_hip(X) and X.shape[0] <= LASSO_CD_MAX_ROWS:
         Xt = getattr(X, "_harmony_xt", None)
         if Xt is None:
             Xt = X.t().contiguous()

@@ -10,8 +10,8 @@
 // WG is the right shape — the op is latency-bound, not throughput-bound.
 //
 // X is passed transposed ([F, B] contiguous) so each coordinate's column
-// is a coalesced stream. B is capped by LDS (<= ~15k samples); larger
-// batches fall back to the torch path in the python wrapper.
+// is a coalesced stream. B is capped by LDS (<= 16367 samples); the binding
+// hands larger batches, up to lasso_cd_max_rows(), to K11L (lasso_large.hip).
 
 #include "hip_common.h"
 
@@ -65,6 +65,11 @@ __global__ void lasso_cd_kernel(const float* __restrict__ Xt,
 
 }  // namespace
 
+int64_t lasso_cd_max_rows();
+void lasso_cd_large_launch(const float* Xt, float* r, float* w,
+                           const float* col_sq, float lam_n, int B, int F,
+                           hipStream_t stream);
+
 void lasso_cd(torch::Tensor Xt, torch::Tensor r, torch::Tensor w,
               torch::Tensor col_sq, double lam_n) {
   check_tensor(__func__, Xt, "Xt", torch::kFloat32, {-1, -1});
@@ -74,9 +79,16 @@ void lasso_cd(torch::Tensor Xt, torch::Tensor r, torch::Tensor w,
   check_tensor(__func__, col_sq, "col_sq", torch::kFloat32, {F});
   check_below_2_31(__func__, {{"F", Xt.size(0)}});
   const size_t lds = (Xt.size(1) + CD_THREADS / WAVE + 1) * sizeof(float);
-  TORCH_CHECK(lds <= 64 * 1024, __func__,
-              ": batch too large for LDS-resident residual");
+  TORCH_CHECK(Xt.size(1) <= lasso_cd_max_rows(), __func__,
+              ": batch too large for a residual kept on chip (max ",
+              lasso_cd_max_rows(), " rows)");
   check_on_device(__func__, {Xt, r, w, col_sq});
+  if (lds > 64 * 1024) {
+    lasso_cd_large_launch(Xt.data_ptr<float>(), r.data_ptr<float>(),
+                          w.data_ptr<float>(), col_sq.data_ptr<float>(),
+                          (float)lam_n, B, F, current_stream());
+    return;
+  }
   hipLaunchKernelGGL(lasso_cd_kernel, dim3(1), dim3(CD_THREADS), lds,
                      current_stream(), Xt.data_ptr<float>(),
                      r.data_ptr<float>(), w.data_ptr<float>(),

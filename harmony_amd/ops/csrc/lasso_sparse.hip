@@ -65,32 +65,6 @@ constexpr int kResidOff = kMaskOff + 2 * kScan * kMaxWaves;
 constexpr int64_t kLdsBytes = 64 * 1024;
 constexpr int64_t kMaxRows = kLdsBytes / 4 - kResidOff;
 
-__device__ __forceinline__ int lane_i(int v, int l) {
-  return __builtin_amdgcn_readlane(v, l);
-}
-__device__ __forceinline__ float lane_f(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-
-// Wave sum that leaves the same bits in every lane, without the LDS crossbar
-// a __shfl_xor butterfly goes through (six dependent ds_bpermute round trips
-// were most of a short column's time): four DPP steps inside each 16-lane
-// row (xor 1, xor 2, half mirror, mirror; each pair of lanes adds the same
-// two values, so a row's lanes agree), then the four row sums by v_readlane.
-// Needs all 64 lanes active.
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(
-                 0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float wave_sum_uniform(float v) {
-  v = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
-  v = dpp_add<0x4E>(v);    // quad_perm [2,3,0,1]
-  v = dpp_add<0x141>(v);   // row_half_mirror
-  v = dpp_add<0x140>(v);   // row_mirror
-  return (lane_f(v, 0) + lane_f(v, 16)) + (lane_f(v, 32) + lane_f(v, 48));
-}
-
 // One column per lane: the scalars of columns k0 .. k0+63.
 struct ColBatch {
   int id;        // feature, -1 where there is no (valid) column

@@ -85,6 +85,7 @@ std::vector<torch::Tensor> lda_foldin(
 int64_t lda_foldin_max_topics();
 void lasso_cd(torch::Tensor Xt, torch::Tensor r, torch::Tensor w,
               torch::Tensor col_sq, double lam_n);
+int64_t lasso_cd_max_rows();
 int64_t lasso_cd_sparse_max_rows();
 void lasso_cd_sparse(torch::Tensor feat_ids, torch::Tensor feat_ptr,
                      torch::Tensor feat_row, torch::Tensor feat_val,
@@ -214,7 +215,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "deepest tree K10p takes");
   m.def("gbt_predict_lds_words", &gbt_predict_lds_words,
         "words of staged trees per LDS group of K10p");
-  m.def("lasso_cd", &lasso_cd, "Lasso persistent CD sweep (K11)");
+  m.def("lasso_cd", &lasso_cd,
+        "Lasso persistent CD sweep (K11; K11L past K11's LDS limit)");
+  m.def("lasso_cd_max_rows", &lasso_cd_max_rows,
+        "largest batch lasso_cd takes");
   m.def("lasso_cd_sparse", &lasso_cd_sparse,
         "Lasso CD sweep over a batch's column index (K11s)");
   m.def("lasso_cd_sparse_max_rows", &lasso_cd_sparse_max_rows,
