@@ -277,10 +277,11 @@ class OneSidedTable(Table):
         lose updates) — f(f(v,d1),d2), the reference's sequential op-queue
         semantics."""
         from harmony_amd import ops as _ops
+        from harmony_amd.et import update_functions as uf
 
-        ua = self.cfg.update_args or {}
-        kw = dict(step_size=float(ua.get("step_size", 0.0)),
-                  max_val=float(ua.get("max_val", 0.0)))
+        step_size, max_val = uf.fused_apply_args(self.cfg.update_fn,
+                                                 self.cfg.update_args)
+        kw = dict(step_size=step_size, max_val=max_val)
         rows = self._rows_on(self.rank, keys)
         order = torch.argsort(rows, stable=True)
         sr = rows[order]

@@ -130,8 +130,8 @@ class Table:
             # fused gather-apply-scatter kernel (K3/K9)
             ops.scatter_apply(self.shard, rows, deltas.to(self.dtype),
                               self.cfg.update_fn,
-                              self.cfg.update_args.get("step_size", 0.0),
-                              self.cfg.update_args.get("max_val", 0.0))
+                              *uf.fused_apply_args(self.cfg.update_fn,
+                                                   self.cfg.update_args))
             return
         fn = uf.update_fn(self.cfg.update_fn)
         vals = self.shard[rows]
@@ -143,8 +143,8 @@ class Table:
         if self.device.type == "cuda" and ops.fused_apply_supported(self.cfg.update_fn):
             ops.dense_apply(self.shard, agg_delta.to(self.dtype),
                             self.cfg.update_fn,
-                            self.cfg.update_args.get("step_size", 0.0),
-                            self.cfg.update_args.get("max_val", 0.0))
+                            *uf.fused_apply_args(self.cfg.update_fn,
+                                                 self.cfg.update_args))
             return
         fn = uf.update_fn(self.cfg.update_fn)
         fn(self.shard, agg_delta.to(self.shard.dtype), **self.cfg.update_args)

@@ -17,6 +17,8 @@ delta-merge associativity.
 
 from __future__ import annotations
 
+import functools
+import inspect
 from typing import Any, Callable, Dict
 
 import torch
@@ -108,6 +110,32 @@ def _update_nmf(values: torch.Tensor, delta: torch.Tensor, step_size: float = 0.
     # clamped to the valid non-negative range).
     values.add_(delta, alpha=-step_size).clamp_(0.0, max_val)
     return values
+
+
+def fused_apply_args(name: str, update_args=None):
+    """(step_size, max_val) that the fused apply kernels (K3/K9,
+    ops.scatter_apply / ops.dense_apply) take for update function `name` and
+    a table's update_args. A missing argument falls back to the default of
+    the torch function above, so both paths compute the same update; a
+    function without that argument ignores it in the kernel too, and gets 0."""
+    given = update_args or {}
+    step_size, max_val = _fused_apply_defaults(name)
+    return (float(given.get("step_size", step_size)),
+            float(given.get("max_val", max_val)))
+
+
+@functools.lru_cache(maxsize=None)
+def _fused_apply_defaults(name: str):
+    # read off the torch function's signature, once per function name
+    params = inspect.signature(update_fn(name)).parameters
+
+    def one(key):
+        p = params.get(key)
+        if p is None or p.default is inspect.Parameter.empty:
+            return 0.0
+        return float(p.default)
+
+    return one("step_size"), one("max_val")
 
 
 @register_update("lda_counts")

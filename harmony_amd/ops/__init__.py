@@ -246,6 +246,8 @@ def mlr_step_mfma(X: torch.Tensor, W: torch.Tensor, labels: torch.Tensor,
         splitf = _pow2_div(max(1, 512 // (rows // 64)), F // 64)
     if splitb is None:
         splitb = _pow2_div(max(1, 512 // (F // 64)), rows // 64)
+        if B % rows:          # a shorter last block must split evenly too
+            splitb = _pow2_div(splitb, (B % rows) // 64)
     if Wt_buf is None:
         Wt_buf = torch.zeros((F, 16), dtype=X.dtype, device=X.device)
     Wt_buf[:, :C] = W.t()

@@ -20,7 +20,10 @@ __device__ __forceinline__ T apply_one(T v, T d, int mode, float step,
     case ASSIGN: return d;
     case NMF_SGD: {
       float x = (float)v - step * (float)d;
-      x = fminf(fmaxf(x, 0.f), maxval);
+      // compares, not fminf/fmaxf: those return the other operand for a
+      // NaN, and a NaN must stay one as under torch's clamp_
+      x = x < 0.f ? 0.f : x;
+      x = x > maxval ? maxval : x;
       return (T)x;
     }
     case LDA_COUNTS: {

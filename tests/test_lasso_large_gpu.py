@@ -11,14 +11,15 @@ four times that. (K11L measured on an MI355X: 1.77e-7 and 8.30e-7 at most,
 profiles/lasso_large_ab.md.)
 """
 
-import functools
-
 import pytest
 import torch
 
+# the cases (features 2 and 4 sit clear of 0 and of lam_n) and the float64
+# sweep are shared with K11's tests
+from tests.lasso_dense_cases import F, make_case, sweep64  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-F = 6
 ROWS = [16368,    # first row count K11 refuses
         16384,    # the habitual batch size; last all-in-16-registers count
         32768,    # all-register boundary
@@ -26,37 +27,8 @@ ROWS = [16368,    # first row count K11 refuses
         40001,    # ragged in the registers' last chunk and in LDS
         65535, 65536]
 LAMS = [0.0, 0.05]            # lam_n = lam * B
-# Features 2 and 4 have c near 0.02 B: clear of 0, and clear of lam_n, under
-# which feature 2 thresholds from 0.3 to exactly 0 and feature 4 stays at 0.
-# The later weights start near the truth so that the residual's noise in
-# those two c stays a tenth of that.
-W_TRUE = [1.5, -2.0, 0.02, 0.8, 0.02, -1.2]
-W_IN = [0.5, -1.0, 0.3, 0.75, 0.0, -1.15]
 W_LOOP_ERR, R_LOOP_ERR = 2.32e-7, 1.51e-6   # measured, see the docstring
 W_TOL, R_TOL = 4 * W_LOOP_ERR, 4 * R_LOOP_ERR
-
-
-@functools.lru_cache(maxsize=None)
-def make_case(B, nf=F):
-    g = torch.Generator().manual_seed(B)
-    X = torch.randn(B, nf, generator=g)
-    y = X @ torch.tensor(W_TRUE[:nf]) + 0.1 * torch.randn(B, generator=g)
-    w = torch.tensor(W_IN[:nf])
-    return dict(X=X, w=w, r=y - X @ w, col_sq=(X * X).sum(dim=0))
-
-
-def sweep64(case, lam_n):
-    """The float64 sweep: (w, r, smallest ||c| - lam_n| over coordinates)."""
-    X, col_sq = case["X"].double(), case["col_sq"].double()
-    w, r = case["w"].double().clone(), case["r"].double().clone()
-    margin = float("inf")
-    for f in range(X.shape[1]):
-        c = X[:, f] @ r + w[f] * col_sq[f]
-        margin = min(margin, abs(float(c.abs()) - lam_n))
-        wn = torch.sign(c) * torch.clamp(c.abs() - lam_n, min=0.0) / col_sq[f]
-        r += X[:, f] * (w[f] - wn)
-        w[f] = wn
-    return w, r, margin
 
 
 def check(case, lam_n, w, r, label):
