@@ -25,7 +25,9 @@ as the reference does (LassoETParser createSparse, horzcatVecSparse at
 LassoTrainer.java:273-283), and runs the K11s sweep (ops/csrc/
 lasso_sparse.hip) over the features PRESENT in the batch: memory and time
 follow the non-zeros, not B * F, so num_features may be far wider than a row
-is long. Pull and push stay dense ([P, F/P]).
+is long. Batches of up to 16208 rows run K11s, from there to 40928 rows
+K11sL (ops/csrc/lasso_sparse_large.hip), larger ones the tensor-op loop.
+Pull and push stay dense ([P, F/P]).
 
 The two paths differ on purpose in one place. The sparse sweep skips a
 feature that has no entries in the batch (or whose column mass is <= 1e-9)
@@ -184,8 +186,8 @@ class LassoTrainer(Trainer):
         F = X.shape[1]
         lam_n = self.a["lam"] * X.shape[0]
         if isinstance(X, SparseBatch):
-            # one K11s sweep over the batch's present features; the
-            # residual is built inside the op
+            # one K11s / K11sL sweep over the batch's present features;
+            # the residual is built inside the op
             w, r = ops.lasso_cd_sparse(X.feat_ids, X.feat_ptr, X.feat_row,
                                        X.feat_val, y, self.w,
                                        _sparse_col_sq(X), lam_n)

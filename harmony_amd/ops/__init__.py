@@ -24,6 +24,8 @@ Kernel inventory (reference hot loops):
   K11 lasso_cd            LassoTrainer.java:164-190
   K11L lasso_cd           K11 for 16368..65536 rows: residual in registers + LDS
   K11s lasso_cd_sparse    LassoTrainer.java:164-208 over SparseVector columns
+  K11sL lasso_cd_sparse   K11s for 16209..40928 rows: 160 KiB of LDS, windows
+                          of row-disjoint columns swept one wave per column
   K12 loss reductions     NMFTrainer.java:414-456 etc.
   K13 pregel_pull         pregel MessageManager.addMessage + MessageCombiner
   K13p pregel_push        K13 along the out-edges of the sending vertices only
@@ -1376,8 +1378,14 @@ def lasso_cd(X: torch.Tensor, r: torch.Tensor, w: torch.Tensor,
 # ---------------------------------------------------------------------------
 
 LASSO_ZERO_THRESHOLD = 1e-9
-# rows K11s keeps in LDS (64 KiB less its scratch; the binding checks it)
-LASSO_SPARSE_MAX_ROWS = 16384 - 176
+# rows K11s keeps in 64 KiB of LDS less its scratch; above, K11sL
+LASSO_SPARSE_K11S_ROWS = 16208
+# rows K11sL keeps in gfx950's 160 KiB of LDS less its scratch (the binding
+# checks it)
+LASSO_SPARSE_MAX_ROWS = 40960 - 32
+# longest column a wave of K11sL sweeps alone (profiles/
+# lasso_sparse_large_ab.md)
+LASSO_SPARSE_SOLO_LEN = 256
 
 
 def lasso_sparse_threads(nf: int, nnz: int) -> int:
@@ -1395,6 +1403,49 @@ def lasso_sparse_threads(nf: int, nnz: int) -> int:
     if mean <= 512:
         return 256
     return 1024
+
+
+def lasso_sparse_large_threads(nf: int, nnz: int) -> int:
+    """Threads of the one K11sL workgroup (batches above
+    LASSO_SPARSE_K11S_ROWS), from the mean column length nnz / nf. A window
+    is threads / 64 columns, so with 64 threads there are no windows and
+    the choice is between 256 and 1024. Up to a mean of 4 entries nearly
+    every window of 16 columns is clean and 16 waves sweep 16 columns at
+    once. Longer columns collide within 16 (40 % clean at a mean of 16) but
+    less often within 4, and are too short to pay for 16 waves' partials
+    when they go one at a time. From a mean of about 192 on every window is
+    dirty and 1024 threads on one column win. Measured at means of 1.1 to
+    1.8, 16, 64, 128, 255 and 319: profiles/lasso_sparse_large_ab.md. A
+    function of the batch alone."""
+    mean = nnz / max(1, nf)
+    return 256 if 4 < mean <= 192 else 1024
+
+
+def lasso_sparse_windows(feat_ptr: torch.Tensor, feat_row: torch.Tensor,
+                         width: int, solo_len: int) -> torch.Tensor:
+    """Clean flags of a column index's windows, uint8 [ceil(nf / width)]:
+    window i is columns i*width .. i*width+width-1, and it is clean (1) when
+    no row occurs in two of its columns and none of them has more than
+    solo_len entries. K11sL sweeps the columns of a clean window side by
+    side, one wave each. Every entry is keyed by (window, row); a window
+    with a repeated key is dirty (rows are distinct within a column, so a
+    repeat is two columns). Tensor ops only, O(nnz log nnz)."""
+    nf, nnz = feat_ptr.shape[0] - 1, feat_row.shape[0]
+    dev = feat_ptr.device
+    nwin = (nf + width - 1) // width
+    lens = feat_ptr[1:] - feat_ptr[:-1]
+    win_of_col = torch.arange(nf, device=dev) // width
+    bad = torch.zeros(nwin, dtype=torch.int64, device=dev)
+    bad.index_add_(0, win_of_col, (lens > solo_len).long())
+    if nnz:
+        rows = feat_row.long()
+        stride = rows.max() + 1
+        key = torch.repeat_interleave(win_of_col, lens,
+                                      output_size=nnz) * stride + rows
+        key = key.sort().values
+        bad.index_add_(0, torch.div(key[1:], stride, rounding_mode="floor"),
+                       (key[1:] == key[:-1]).long())
+    return (bad == 0).to(torch.uint8)
 
 
 def lasso_cd_sparse(feat_ids: torch.Tensor, feat_ptr: torch.Tensor,
@@ -1420,21 +1471,46 @@ def lasso_cd_sparse(feat_ids: torch.Tensor, feat_ptr: torch.Tensor,
     from the batch. Returns (w_new, r_new) with r_new = y - X w_new; inputs
     are not mutated.
 
+    GPU: one workgroup behind one binding. Up to LASSO_SPARSE_K11S_ROWS
+    rows K11s keeps the residual in 64 KiB of LDS; from there to
+    LASSO_SPARSE_MAX_ROWS rows K11sL (ops/csrc/lasso_sparse_large.hip) keeps
+    it in up to 160 KiB and sweeps windows of threads / 64 consecutive
+    columns that share no row side by side, one wave per column, by the
+    table of lasso_sparse_windows. The table is built once per column index
+    and thread count and kept on the feat_ptr tensor (a batch is static,
+    and SparseBatch.prefix() and .to() make new tensors). K11sL's sums are
+    ordered differently from K11s's; each is bitwise reproducible.
+
     CPU tensors, HARMONY_FORCE_TORCH_OPS=1 and batches above
     LASSO_SPARSE_MAX_ROWS take the torch loop below, which is the reference
-    implementation. _force_threads overrides lasso_sparse_threads (tests)."""
+    implementation. _force_threads overrides lasso_sparse_threads and
+    lasso_sparse_large_threads (tests)."""
     B, nf = y.shape[0], feat_ids.shape[0]
     w = w.clone()
     if B == 0 or nf == 0:
         return w, y.clone()
     if _use_hip(y) and B <= LASSO_SPARSE_MAX_ROWS:
-        threads = _force_threads or lasso_sparse_threads(
-            nf, feat_row.shape[0])
+        large = B > LASSO_SPARSE_K11S_ROWS
+        threads = int(_force_threads or (
+            lasso_sparse_large_threads if large else lasso_sparse_threads)(
+                nf, feat_row.shape[0]))
+        windows = None
+        if large and threads > 64:
+            cache = getattr(feat_ptr, "_harmony_windows", None)
+            if cache is None:
+                cache = feat_ptr._harmony_windows = {}
+            key = (threads // 64, LASSO_SPARSE_SOLO_LEN)
+            if key not in cache:
+                table = lasso_sparse_windows(feat_ptr, feat_row, *key)
+                # no clean window (one host read per column index): without
+                # a table the kernel does not look any flags up
+                cache[key] = table if bool(table.any()) else None
+            windows = cache[key]
         r = torch.empty_like(y)
         _hip.lasso_cd_sparse(
             feat_ids.contiguous(), feat_ptr.contiguous(),
             feat_row.contiguous(), feat_val.contiguous(), y.contiguous(), w,
-            col_sq.contiguous(), float(lam_n), r, int(threads))
+            col_sq.contiguous(), float(lam_n), r, threads, windows)
         return w, r
     r = y.clone()
     ids = feat_ids.tolist()

@@ -15,6 +15,12 @@ inline hipStream_t current_stream() {
   return c10::hip::getCurrentHIPStream().stream();
 }
 
+// A runtime call or a launch (hipGetLastError()) that must have succeeded.
+inline void check_hip(const char* op, hipError_t status, const char* what) {
+  TORCH_CHECK(status == hipSuccess, op, ": ", what, " failed: ",
+              hipGetErrorString(status));
+}
+
 // Full-wave sum: butterfly over 64 lanes; every lane ends with the total.
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll

@@ -296,15 +296,28 @@ __global__ __launch_bounds__(T) void lasso_cd_sparse_kernel(
 
 }  // namespace
 
-// The largest batch the LDS-resident residual admits.
-int64_t lasso_cd_sparse_max_rows() { return kMaxRows; }
+// K11sL (lasso_sparse_large.hip): batches past kMaxRows
+int64_t lasso_cd_sparse_large_max_rows();
+void lasso_cd_sparse_large_launch(
+    const char* op, const int* feat_ids, const int64_t* feat_ptr,
+    const int* feat_row, const float* feat_val, const float* y, float* w,
+    const float* col_sq, const unsigned char* win, float lam_n, float* r_out,
+    int64_t B, int64_t F, int64_t nf, int64_t nnz, int64_t threads);
+
+// The largest batch the LDS-resident residual admits (K11sL's).
+int64_t lasso_cd_sparse_max_rows() { return lasso_cd_sparse_large_max_rows(); }
 
 // One cyclic sweep over the present features. w [F] is updated in place,
-// r_out [B] receives y - X w_new. threads: 64, 256 or 1024.
+// r_out [B] receives y - X w_new. threads: 64, 256 or 1024. Up to 16208 rows
+// K11s runs and windows is ignored; above, K11sL, with windows (uint8, one
+// flag per threads / 64 consecutive columns, 1: the columns share no row and
+// may be swept side by side; trusted, not verified) or with every window
+// taken as dirty when there is none.
 void lasso_cd_sparse(torch::Tensor feat_ids, torch::Tensor feat_ptr,
                      torch::Tensor feat_row, torch::Tensor feat_val,
                      torch::Tensor y, torch::Tensor w, torch::Tensor col_sq,
-                     double lam_n, torch::Tensor r_out, int64_t threads) {
+                     double lam_n, torch::Tensor r_out, int64_t threads,
+                     c10::optional<torch::Tensor> windows) {
   check_tensor(__func__, feat_ids, "feat_ids", torch::kInt32, {-1});
   const int64_t nf = feat_ids.numel();
   check_tensor(__func__, feat_ptr, "feat_ptr", torch::kInt64, {nf + 1});
@@ -318,14 +331,26 @@ void lasso_cd_sparse(torch::Tensor feat_ids, torch::Tensor feat_ptr,
   const int64_t F = w.numel();
   check_tensor(__func__, col_sq, "col_sq", torch::kFloat32, {nf});
   TORCH_CHECK(nf >= 1 && B >= 1, __func__, ": empty batch");
-  TORCH_CHECK(B <= kMaxRows, __func__, ": batch too large for LDS-resident "
-              "residual (max ", kMaxRows, " rows)");
+  const int64_t max_rows = lasso_cd_sparse_large_max_rows();
+  TORCH_CHECK(B <= max_rows, __func__, ": batch too large for LDS-resident "
+              "residual (max ", max_rows, " rows)");
   check_below_2_31(__func__, {{"nnz", nnz}, {"F", F},
                         {"nf (padded to the scan width)",
                          nf + 4 * 1024 * kScan}});
   check_pow2<64, 1024, 4>(__func__, "threads", threads);
+  const int64_t nw = threads / WAVE;
+  const unsigned char* win = check_tensor<unsigned char>(
+      __func__, windows, "windows", {(nf + nw - 1) / nw});
   check_on_device(__func__, {feat_ids, feat_ptr, feat_row, feat_val, y, w,
-                             col_sq, r_out});
+                             col_sq, r_out, windows});
+  if (B > kMaxRows) {
+    lasso_cd_sparse_large_launch(
+        __func__, feat_ids.data_ptr<int>(), feat_ptr.data_ptr<int64_t>(),
+        feat_row.data_ptr<int>(), feat_val.data_ptr<float>(),
+        y.data_ptr<float>(), w.data_ptr<float>(), col_sq.data_ptr<float>(),
+        win, (float)lam_n, r_out.data_ptr<float>(), B, F, nf, nnz, threads);
+    return;
+  }
   const size_t lds = (size_t)(kResidOff + B) * sizeof(float);
   dispatch_pow2<64, 1024, 4>(__func__, "threads", threads, [&](auto t) {
     hipLaunchKernelGGL(

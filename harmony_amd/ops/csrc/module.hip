@@ -90,7 +90,8 @@ int64_t lasso_cd_sparse_max_rows();
 void lasso_cd_sparse(torch::Tensor feat_ids, torch::Tensor feat_ptr,
                      torch::Tensor feat_row, torch::Tensor feat_val,
                      torch::Tensor y, torch::Tensor w, torch::Tensor col_sq,
-                     double lam_n, torch::Tensor r_out, int64_t threads);
+                     double lam_n, torch::Tensor r_out, int64_t threads,
+                     c10::optional<torch::Tensor> windows);
 torch::Tensor os_shard_alloc(int64_t rows, int64_t k, int64_t dtype_i32);
 torch::Tensor os_ipc_handle(torch::Tensor shard);
 int64_t os_ipc_open(torch::Tensor handle_bytes);
@@ -220,9 +221,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lasso_cd_max_rows", &lasso_cd_max_rows,
         "largest batch lasso_cd takes");
   m.def("lasso_cd_sparse", &lasso_cd_sparse,
-        "Lasso CD sweep over a batch's column index (K11s)");
+        "Lasso CD sweep over a batch's column index (K11s; K11sL past "
+        "K11s's LDS limit, with the clean-window table if given)",
+        py::arg("feat_ids"), py::arg("feat_ptr"), py::arg("feat_row"),
+        py::arg("feat_val"), py::arg("y"), py::arg("w"), py::arg("col_sq"),
+        py::arg("lam_n"), py::arg("r_out"), py::arg("threads"),
+        py::arg("windows") = py::none());
   m.def("lasso_cd_sparse_max_rows", &lasso_cd_sparse_max_rows,
-        "largest batch K11s keeps in LDS");
+        "largest batch lasso_cd_sparse keeps in LDS (K11sL's)");
   m.def("os_shard_alloc", &os_shard_alloc, "one-sided shard (hipMalloc)");
   m.def("os_ipc_handle", &os_ipc_handle, "export shard via hipIpc");
   m.def("os_ipc_open", &os_ipc_open, "map a peer shard (xGMI)");
