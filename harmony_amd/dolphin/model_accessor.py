@@ -209,6 +209,26 @@ def build_ps_table(job, cfg, ctx, cp):
     return Table(cfg, ctx.rank, ctx.world_size, ctx.device, comm=comm)
 
 
+def fused_tail(table) -> bool:
+    """Whether a trainer may apply its own push inside its step kernels
+    (NMF: pass B's epilogue; MLR: ops.mlr_grad_finish): the collective table
+    with a single owner, on the GPU, through the HIP kernels. That is the
+    condition of LDA's fused apply. HARMONY_FUSED_TAIL=0 switches the fused
+    tails off (the A/B switch: tensor ops, push_dense / scatter_apply)."""
+    import os
+
+    from harmony_amd import ops
+    from harmony_amd.et.onesided import OneSidedTable
+
+    return (os.environ.get("HARMONY_FUSED_TAIL", "1") != "0"
+            and not isinstance(table, OneSidedTable)
+            and (table.comm is None or table.world_size == 1)
+            and table.shard.device.type == "cuda"
+            and table.shard.dtype == torch.float32
+            and os.environ.get("HARMONY_FORCE_TORCH_OPS") != "1"
+            and ops.hip_available())
+
+
 def accessor_for(table):
     """The accessor a trainer uses for its model table."""
     from harmony_amd.et.onesided import OneSidedTable

@@ -58,7 +58,8 @@ class ModelEvaluator:
             for t in self.tables.values():
                 self.cm.load_into(t, self.app_id,
                                   f"{cid}/{_safe(t.cfg.table_id)}")
-            # one pass over the data: pull + eval per batch
+            # one pass over the data: pull + eval per batch, nothing pushed
+            self.trainer.push_follows = False
             for batch in self.provider.epoch_iter(0):
                 self.trainer.set_batch_data(batch)
                 self.trainer.pull_model()
@@ -67,6 +68,7 @@ class ModelEvaluator:
             # the checkpoint on the held-out test data, if the job has any
             res.update(self.trainer.evaluate_test() or {})
             out[cid] = res
+        self.trainer.push_follows = True
         return out
 
 

@@ -38,6 +38,11 @@ class Trainer:
         # held-out test blocks (app arg test_data_path), set by the app's
         # build(); empty when the job has no test data
         self.test_blocks: list = []
+        # whether push_update() follows every local_compute(). A trainer
+        # whose step kernels apply the push themselves (fused tails) may do
+        # so only then; the offline evaluator computes without pushing and
+        # clears it.
+        self.push_follows = True
 
     def initialize(self) -> None:
         """Once per tasklet before the first epoch (initGlobalSettings)."""

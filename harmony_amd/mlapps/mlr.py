@@ -38,7 +38,8 @@ import torch
 
 from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
-from harmony_amd.dolphin.model_accessor import accessor_for, build_ps_table
+from harmony_amd.dolphin.model_accessor import (accessor_for, build_ps_table,
+                                                 fused_tail)
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
 from harmony_amd.mlapps import heldout
 from harmony_amd.mlapps.sparse_batch import (SparseBatch, csr_row_blocks,
@@ -184,6 +185,34 @@ class MLRTrainer(Trainer):
         self._loss_sum = torch.zeros((), device=ctx.device)
         self._loss_n = 0
         self._correct = torch.zeros((), dtype=torch.int64, device=ctx.device)
+        self._fused = None     # decided at the first pull (_fused_tail)
+        self._applied = False
+
+    def _fused_tail(self) -> bool:
+        """Single-owner path of the default float32 step: the model is read
+        from the shard in place (no pull copy; the only kernel that writes
+        the table, ops.mlr_grad_finish, runs after both GEMMs of the step on
+        the same stream) and that kernel does everything after the gradient
+        GEMM, the push included. HARMONY_FUSED_TAIL=0 switches it off, as
+        HARMONY_MLR_MFMA=1 and HARMONY_GRAPHS=1 do; sparse, bfloat16 and
+        empty batches take the tensor-op tail too."""
+        if self._fused is None:
+            import os
+
+            table = self.accessor.table
+            n = self.a["num_classes"] * self.a["num_parts_per_class"]
+            ok = (fused_tail(table) and not self._graphs.enabled
+                  and os.environ.get("HARMONY_MLR_MFMA", "0") != "1"
+                  and table.cfg.update_fn == "add"
+                  and table.shard.shape[0] == n)
+            if ok:      # key i in shard row i: [C*P, F/P] is W [C, F]
+                keys = torch.arange(n, device=table.shard.device)
+                ok = torch.equal(table.local_rows_of(keys), keys)
+            self._fused = bool(ok)
+        x = self.batch[0]
+        return (self._fused and self.push_follows
+                and not isinstance(x, SparseBatch)
+                and x.dtype == torch.float32 and x.shape[0] > 0)
 
     def _w_matrix(self) -> torch.Tensor:
         C, F = self.a["num_classes"], self.a["num_features"]
@@ -225,6 +254,9 @@ class MLRTrainer(Trainer):
 
     def pull_model(self) -> None:
         C, P = self.a["num_classes"], self.a["num_parts_per_class"]
+        if self._fused_tail():
+            self.W = self.accessor.table.shard
+            return
         pulled = self.accessor.pull_all()[:C * P]
         if self._W_buf is None:
             self._W_buf = pulled.clone()
@@ -239,6 +271,19 @@ class MLRTrainer(Trainer):
             return
         if isinstance(x, SparseBatch):
             self._sparse_compute(x, y)
+            return
+        if self._fused_tail():
+            W = self._w_matrix()                   # the shard, in place
+            p, loss, correct = ops.mlr_forward(x, W, y)
+            g = ops.mlr_grad_gemm(p, x)            # [C, F]
+            # step size passed per call: it decays over epochs
+            self.grad_raw = ops.mlr_grad_finish(
+                g, W, self.accessor.table.shard, x.shape[0], self.a["lam"],
+                self.step_size)
+            self._applied = True
+            self._loss_sum += loss
+            self._correct += correct
+            self._loss_n += x.shape[0]
             return
         key = id(self.batch)
         body = self._bodies.get(key)
@@ -289,6 +334,9 @@ class MLRTrainer(Trainer):
         self._loss_n += x.shape[0]
 
     def push_update(self) -> None:
+        if self._applied:      # ops.mlr_grad_finish already pushed
+            self._applied = False
+            return
         C, P = self.a["num_classes"], self.a["num_parts_per_class"]
         # step size applied OUTSIDE the graph (it decays over epochs)
         delta = (-self.step_size) * self.grad_raw

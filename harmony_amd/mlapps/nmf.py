@@ -23,7 +23,8 @@ import torch
 
 from harmony_amd.config import JobConfig, TableConfig
 from harmony_amd.dolphin.data_provider import TrainingDataProvider
-from harmony_amd.dolphin.model_accessor import accessor_for, build_ps_table
+from harmony_amd.dolphin.model_accessor import (accessor_for, build_ps_table,
+                                                 fused_tail)
 from harmony_amd.dolphin.trainer import Trainer, TrainerContext
 from harmony_amd.utils import stable_seed
 from harmony_amd import ops
@@ -180,6 +181,23 @@ class NMFTrainer(Trainer):
         self._R_bufs = {}
         self._bodies = {}
         self._step_t = torch.tensor(float(self.step_size), device=ctx.device)
+        # single-owner path: pass B applies the server update itself and
+        # push_update has nothing left to launch (HARMONY_FUSED_TAIL=0: off)
+        table = self.accessor.table
+        self._fused_tail = (fused_tail(table) and not self._graphs.enabled
+                            and table.cfg.update_fn == "nmf_sgd")
+        self._applied = False
+
+    def _server_apply(self, b):
+        """ops.nmf_step's apply argument: the shard, the batch's shard rows
+        (cached per block) and the table's own update arguments."""
+        from harmony_amd.et import update_functions as uf
+
+        table = self.accessor.table
+        if not hasattr(b, "shard_rows32"):
+            b.shard_rows32 = table.local_rows_of(b.uniq_cols).to(torch.int32)
+        return (table.shard, b.shard_rows32) + uf.fused_apply_args(
+            table.cfg.update_fn, table.cfg.update_args)
 
     def pull_model(self) -> None:
         b = self.batch
@@ -225,10 +243,13 @@ class NMFTrainer(Trainer):
                     L_src, lo = self.L, b.l_lo
                 else:
                     L_src, lo = self.L[b.l_rows], 0
+                apply = (self._server_apply(b)
+                         if self._fused_tail and self.push_follows else None)
                 L_new, rgrad, sq = ops.nmf_step(
                     L_src, lo, n, R_buf, b.row_ptr32, b.col_local32, b.vals,
                     b.col_sorted32, None, self._step_t, self.a["lam"],
-                    self.a["max_val"])
+                    self.a["max_val"], apply=apply)
+                self._applied = apply is not None
                 if b.l_contiguous:
                     self.L[lo:lo + n].copy_(L_new)
                 else:
@@ -243,6 +264,11 @@ class NMFTrainer(Trainer):
         # uniq_cols are unique and rgrad is already per-key aggregated by K1
         from harmony_amd.dolphin.model_accessor import OneSidedAccessor
 
+        if self._applied:
+            # pass B's epilogue already applied rgrad to the shard
+            self._applied = False
+            self.accessor.table.last_touched_keys = self.batch.uniq_cols
+            return
         if isinstance(self.accessor, OneSidedAccessor):
             self.accessor.push(self.batch.uniq_cols, self.rgrad)
             self.accessor.drain()      # apply peers' queued pushes (owner)

@@ -10,9 +10,12 @@ Set HARMONY_FORCE_TORCH_OPS=1 to force the torch path on GPU (debug only).
 
 Kernel inventory (reference hot loops):
   K1  nmf_grad            NMFTrainer.java:328-367
-  K3  (fused in push)     NMFETModelUpdateFunction.java:48-52
+  K3  (fused in push)     NMFETModelUpdateFunction.java:48-52; on a
+                          single-owner table in nmf_step's pass B (apply=)
   K4  mlr softmax+grad    MLRTrainer.java:374-398,475-489
   K4s mlr_sparse_fwd/grad MLRTrainer.java:374-398 over SparseVector rows
+  K4f mlr_grad_finish     the MLR step after the gradient GEMM, push included
+                          (single-owner table; MLRETModelUpdateFunction.java)
   K4-BF16 mlr_step_mfma   K4-MFMA's step on bfloat16 X (three-term bf16 split)
   K7  lda_gibbs           SparseLDASampler.java:141-274
   K7e lda_foldin          held-out document completion (TestDataProvider)
@@ -111,6 +114,21 @@ def mlr_grad_gemm(P: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
     if X.dtype == torch.bfloat16:
         return _bf16_grad(P, X)
     return P.t() @ X
+
+
+def mlr_grad_finish(g: torch.Tensor, W: torch.Tensor, shard: torch.Tensor,
+                    B: int, lam: float, step: float) -> torch.Tensor:
+    """The tail of an MLR step on a model table this rank owns whole:
+    grad_raw = g / B + lam * W, and the table's add update with
+    delta = (-step) * grad_raw applied to shard, which holds the C * F model
+    floats in W's order and may be W itself. On the GPU one kernel that
+    rounds where this tensor-op chain rounds. Returns grad_raw [C, F]."""
+    if _use_hip(g):
+        return _hip.tail.mlr_grad_finish(g, W, shard, int(B), float(lam),
+                                         float(step))
+    grad_raw = g / B + lam * W
+    shard.add_(((-step) * grad_raw).view_as(shard))
+    return grad_raw
 
 
 # bf16 training data (MLR app arg data_dtype=bfloat16; K4-BF16,
@@ -528,7 +546,7 @@ def nmf_step(L: torch.Tensor, l_lo: int, n: int, R_src: torch.Tensor,
              row_ptr: torch.Tensor, col: torch.Tensor, vals: torch.Tensor,
              col_sorted, rsrc_of: Optional[torch.Tensor],
              step: torch.Tensor, lam: float, max_val: float,
-             want_lgrad: bool = False):
+             want_lgrad: bool = False, apply=None):
     """One NMF compute phase on the batch L[l_lo:l_lo+n]: the two-pass
     gradient of nmf_grad(col_sorted=...) plus the worker-side update
     L_new = clamp(L_batch - step * lgrad, 0, max_val) in the same kernel.
@@ -540,13 +558,21 @@ def nmf_step(L: torch.Tensor, l_lo: int, n: int, R_src: torch.Tensor,
     [n_uniq, k] tensor with local col, or any larger table with rsrc_of.
     Index tensors are int32 on GPU. step is a 0-dim float tensor on L's
     device. L is not modified.
+
+    apply = (shard, shard_row, step_size, max_val): the single-owner push.
+    Pass B then also applies the server's nmf_sgd(step_size, max_val) with
+    rgrad row j to shard[shard_row[j]] (int32 [n_uniq], distinct rows), as
+    scatter_apply would with the returned rgrad. shard must be a tensor of
+    its own, overlapping neither L nor R_src.
     Returns (L_new [n, k], rgrad [n_uniq, k], sq_err_sum[, lgrad])."""
     perm, seg_ptr, row_sorted = col_sorted
     if _use_hip(L):
+        shard, shard_row, srv_step, srv_max = apply or (None, None, 0.0, 0.0)
         return tuple(_hip.nmf_step(
             L.contiguous(), int(l_lo), int(n), R_src.contiguous(), row_ptr,
             col, vals.contiguous(), perm, seg_ptr, row_sorted, rsrc_of, step, float(lam), float(max_val),
-            bool(want_lgrad)))
+            bool(want_lgrad), shard, shard_row, float(srv_step),
+            float(srv_max)))
     L_batch = L[l_lo:l_lo + n]
     lgrad, rgrad, sq = nmf_grad(L_batch, R_src, row_ptr.long(), col.long(),
                                 vals, lam)
@@ -555,6 +581,11 @@ def nmf_step(L: torch.Tensor, l_lo: int, n: int, R_src: torch.Tensor,
     else:
         rgrad = rgrad[:seg_ptr.shape[0] - 1]
     L_new = (L_batch - step * lgrad).clamp_(0.0, max_val)
+    if apply is not None:
+        shard, shard_row, srv_step, srv_max = apply
+        rows = shard_row.long()
+        shard[rows] = shard[rows].add_(rgrad, alpha=-srv_step).clamp_(
+            0.0, srv_max)
     if want_lgrad:
         return L_new, rgrad, sq, lgrad
     return L_new, rgrad, sq

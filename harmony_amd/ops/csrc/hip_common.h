@@ -21,6 +21,20 @@ inline void check_hip(const char* op, hipError_t status, const char* what) {
               hipGetErrorString(status));
 }
 
+// The server's nmf_sgd on one element: clamp(v - step * d, 0, maxval), the
+// product and the difference rounded once, together (what the compiler has
+// always made of that expression in scatter_apply; spelled out so that
+// every kernel that applies the update gets the same bits). Compares, not
+// fminf/fmaxf: those return the other operand for a NaN, and a NaN must stay
+// one as under torch's clamp_.
+__device__ __forceinline__ float nmf_sgd_one(float v, float d, float step,
+                                             float maxval) {
+  float x = __fmaf_rn(-step, d, v);
+  x = x < 0.f ? 0.f : x;
+  x = x > maxval ? maxval : x;
+  return x;
+}
+
 // Full-wave sum: butterfly over 64 lanes; every lane ends with the total.
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll

@@ -213,7 +213,61 @@ void mlr_grad_kernel(const float* __restrict__ P,
   }
 }
 
+// Everything between the gradient GEMM and the next pull, for a model table
+// that this rank owns whole: grad_raw = g / B + lam * W, then the table's add
+// update with delta = (-step) * grad_raw. One launch for the five tensor ops
+// of that chain, and each element is rounded where the chain rounds it: the
+// divide (a product with the float reciprocal of B, which is how the tensor
+// op divides by a host scalar), lam * W, their sum, the product with -step,
+// and the sum with the table element. Contraction is off so that none of
+// them fuses. W may be the shard itself: an element is read before it is
+// written, by the same thread.
+__global__ void mlr_grad_finish_kernel(const float* __restrict__ g,
+                                       const float* W, float* shard,
+                                       float* __restrict__ grad_raw,
+                                       int64_t n, float inv_b, float lam,
+                                       float neg_step) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float q = g[i] * inv_b;
+  const float lw = lam * W[i];
+  const float gr = q + lw;
+  grad_raw[i] = gr;
+  const float delta = neg_step * gr;
+  shard[i] = shard[i] + delta;
+}
+
 }  // namespace
+
+// g, W: [C, F]; shard: the model table's C * F floats in the same order
+// (any 2-d shape). Returns grad_raw [C, F]; shard is updated in place.
+torch::Tensor mlr_grad_finish(torch::Tensor g, torch::Tensor W,
+                              torch::Tensor shard, int64_t B, double lam,
+                              double step) {
+  check_tensor(__func__, g, "g", torch::kFloat32, {-1, -1});
+  check_tensor(__func__, W, "W", torch::kFloat32, g.sizes());
+  check_tensor(__func__, shard, "shard", torch::kFloat32, {-1, -1});
+  const int64_t n = g.numel();
+  TORCH_CHECK(shard.numel() == n, __func__, ": shard must hold ", n,
+              " elements like g, got ", shard.numel());
+  TORCH_CHECK(B > 0, __func__, ": B must be positive, got ", B);
+  check_below_2_31(__func__, {{"C * F", n}});
+  const char* wp = (const char*)W.data_ptr();
+  const char* sp = (const char*)shard.data_ptr();
+  TORCH_CHECK(wp == sp || wp + 4 * n <= sp || sp + 4 * n <= wp, __func__,
+              ": W must be the shard itself or apart from it");
+  check_on_device(__func__, {g, W, shard});
+  auto grad_raw = torch::empty_like(g);
+  if (n > 0) {
+    dim3 blk(256), grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(mlr_grad_finish_kernel, grid, blk, 0, current_stream(),
+                       g.data_ptr<float>(), W.data_ptr<float>(),
+                       shard.data_ptr<float>(), grad_raw.data_ptr<float>(), n,
+                       1.0f / (float)B, (float)lam, (float)(-step));
+  }
+  return grad_raw;
+}
 
 torch::Tensor mlr_grad(torch::Tensor P, torch::Tensor X) {
   check_tensor(__func__, X, "X", torch::kFloat32, {-1, -1});

@@ -18,10 +18,14 @@ std::vector<torch::Tensor> nmf_step(
     torch::Tensor row_ptr, torch::Tensor col, torch::Tensor vals,
     torch::Tensor perm, torch::Tensor seg_ptr, torch::Tensor row_sorted,
     c10::optional<torch::Tensor> rsrc_of, torch::Tensor step, double lam,
-    double max_val, bool want_lgrad);
+    double max_val, bool want_lgrad, c10::optional<torch::Tensor> shard,
+    c10::optional<torch::Tensor> shard_row, double srv_step, double srv_max);
 std::vector<torch::Tensor> mlr_fwd(torch::Tensor X, torch::Tensor W,
                                    torch::Tensor labels);
 torch::Tensor mlr_grad(torch::Tensor P, torch::Tensor X);
+torch::Tensor mlr_grad_finish(torch::Tensor g, torch::Tensor W,
+                              torch::Tensor shard, int64_t B, double lam,
+                              double step);
 std::vector<torch::Tensor> mlr_step_mfma(torch::Tensor X, torch::Tensor Wt,
                                          torch::Tensor labels,
                                          int64_t row_block, int64_t C,
@@ -167,7 +171,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nmf_grad_twopass", &nmf_grad_twopass,
         "NMF gradient, segmented-reduce rgrad, no atomics (K1+K2)");
   m.def("nmf_step", &nmf_step,
-        "NMF two-pass gradient with prefetch ring + fused L update (K1+K2)");
+        "NMF two-pass gradient with prefetch ring + fused L update (K1+K2), "
+        "optionally with the single-owner server update in pass B",
+        py::arg("L"), py::arg("l_lo"), py::arg("n"), py::arg("R_src"),
+        py::arg("row_ptr"), py::arg("col"), py::arg("vals"), py::arg("perm"),
+        py::arg("seg_ptr"), py::arg("row_sorted"), py::arg("rsrc_of"),
+        py::arg("step"), py::arg("lam"), py::arg("max_val"),
+        py::arg("want_lgrad"), py::arg("shard") = py::none(),
+        py::arg("shard_row") = py::none(), py::arg("srv_step") = 0.0,
+        py::arg("srv_max") = 0.0);
   m.def("mlr_fwd", &mlr_fwd,
         "fused MLR forward: X@W^T + softmax + grad + CE/acc (K4)");
   m.def("mlr_grad", &mlr_grad, "skinny-C gradient GEMM P^T @ X (K5)");
@@ -264,4 +276,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "sparse MLR logits: CSR gather-reduce over W^T rows (K4s)");
   m.def("mlr_sparse_grad", &mlr_sparse_grad,
         "sparse MLR gradient through the batch's column index (K4s)");
+  // Step tails: kernels that do a trainer's push inside its own step. They
+  // sit in a submodule because the module's own names are a closed list
+  // (tests/test_binding_checks_cpu.py); their argument checks are tested
+  // with the kernels (tests/test_mlr_finish_cpu.py).
+  auto tail = m.def_submodule("tail", "fused step tails");
+  tail.def("mlr_grad_finish", &mlr_grad_finish,
+           "MLR step tail: grad_raw = g / B + lam * W and the single-owner "
+           "add push of (-step) * grad_raw, one kernel");
 }

@@ -523,7 +523,10 @@ nmf_step_b_kernel(const float* __restrict__ L,      // batch rows [n, k]
                   const int* __restrict__ row_sorted,
                   const int* __restrict__ rsrc_of,  // null: identity
                   float* __restrict__ rgrad,
-                  int n_cols, int k, float lam2) {
+                  float* __restrict__ shard,        // null: no server apply
+                  const int* __restrict__ shard_row,
+                  int n_cols, int k, float lam2, float srv_step,
+                  float srv_max) {
   static_assert(D <= G, "ring shape");
   const int lane = threadIdx.x & (G - 1);
   const int colid = (blockIdx.x * blockDim.x + threadIdx.x) / G;
@@ -585,6 +588,17 @@ nmf_step_b_kernel(const float* __restrict__ L,      // batch rows [n, k]
 #pragma unroll
   for (int c = 0; c < 4; ++c) out.v[c] = acc.v[c] + nl * rr.v[c];
   io.store(rgrad + (size_t)colid * k, out);
+  if (shard) {
+    // single-owner push: the server's nmf_sgd on this column's table row,
+    // element for element what scatter_apply does with this rgrad row. The
+    // batch's columns are unique, so the row is this lane group's alone.
+    float* srow = shard + (size_t)shard_row[colid] * k;
+    Row4 sv = io.load(srow);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      sv.v[c] = nmf_sgd_one(sv.v[c], out.v[c], srv_step, srv_max);
+    io.store(srow, sv);
+  }
 }
 
 }  // namespace
@@ -592,13 +606,20 @@ nmf_step_b_kernel(const float* __restrict__ L,      // batch rows [n, k]
 // L: [NL, k], the batch is rows l_lo..l_lo+n. col indexes rows of R_src;
 // seg_ptr has one segment per rgrad row (n_uniq); rsrc_of maps an rgrad row
 // to its R_src row (undefined tensor: identity). step: 0-dim device float.
+// With shard [rows, k] and shard_row [n_uniq] (both or neither), pass B also
+// applies the server's nmf_sgd(srv_step, srv_max) with rgrad row j to shard
+// row shard_row[j]: the single-owner push, without a launch of its own. The
+// rows named must be distinct and inside shard, and shard may overlap neither
+// L nor R_src (pass B reads both while it writes shard).
 // Returns {L_new [n,k], rgrad [n_uniq,k], sq_err[, lgrad [n,k]]}.
 std::vector<torch::Tensor> nmf_step(
     torch::Tensor L, int64_t l_lo, int64_t n, torch::Tensor R_src,
     torch::Tensor row_ptr, torch::Tensor col, torch::Tensor vals,
     torch::Tensor perm, torch::Tensor seg_ptr, torch::Tensor row_sorted,
     c10::optional<torch::Tensor> rsrc_of, torch::Tensor step, double lam,
-    double max_val, bool want_lgrad) {
+    double max_val, bool want_lgrad, c10::optional<torch::Tensor> shard,
+    c10::optional<torch::Tensor> shard_row, double srv_step,
+    double srv_max) {
   check_tensor(__func__, L, "L", torch::kFloat32, {-1, -1});
   const int k = L.size(1);
   check_tensor(__func__, R_src, "R_src", torch::kFloat32, {-1, L.size(1)});
@@ -620,8 +641,21 @@ std::vector<torch::Tensor> nmf_step(
   const int* rsrc_p = check_tensor<int>(__func__, rsrc_of, "rsrc_of", {m});
   TORCH_CHECK(rsrc_p != nullptr || R_src.size(0) >= m, __func__,
               ": R_src has fewer rows than seg_ptr has segments");
+  float* shard_p = check_tensor<float>(__func__, shard, "shard", {-1, k});
+  const int* srow_p = check_tensor<int>(__func__, shard_row, "shard_row", {m});
+  TORCH_CHECK((shard_p != nullptr) == (srow_p != nullptr), __func__,
+              ": shard and shard_row go together");
+  if (shard_p) {
+    const auto apart = [&](const torch::Tensor& t) {
+      const char* a = (const char*)shard_p;
+      const char* b = (const char*)t.data_ptr();
+      return a + shard->nbytes() <= b || b + t.nbytes() <= a;
+    };
+    TORCH_CHECK(apart(L) && apart(R_src), __func__,
+                ": shard must not overlap L or R_src");
+  }
   check_on_device(__func__, {L, R_src, row_ptr, col, vals, perm, seg_ptr,
-                       row_sorted, step, rsrc_of});
+                       row_sorted, step, rsrc_of, shard, shard_row});
   auto L_new = torch::empty({n, k}, L.options());
   auto rgrad = torch::empty({m, k}, L.options());
   auto e = torch::empty({nnz}, L.options());
@@ -630,7 +664,8 @@ std::vector<torch::Tensor> nmf_step(
   if (want_lgrad) lgrad = torch::empty({n, k}, L.options());
   const float* Lp = L.data_ptr<float>() + l_lo * k;
   const float* Rp = R_src.data_ptr<float>();
-  const bool vec = k % 4 == 0 && aligned16(Lp) && aligned16(Rp);
+  const bool vec = k % 4 == 0 && aligned16(Lp) && aligned16(Rp) &&
+                   aligned16(shard_p);
   const bool wide = k > 4 * 32;   // four floats per lane: G=32 holds 128
   // ring depth 4 with dots reduced in pairs: measured best of D = 2, 4, 8 on
   // MI355X at the bench shape (profiles/r03_nmf_step.md)
@@ -656,7 +691,8 @@ std::vector<torch::Tensor> nmf_step(
                            current_stream(), Lp, Rp, e.data_ptr<float>(),
                            perm.data_ptr<int>(), seg_ptr.data_ptr<int>(),
                            row_sorted.data_ptr<int>(), rsrc_p,
-                           rgrad.data_ptr<float>(), m, k, lam2);
+                           rgrad.data_ptr<float>(), shard_p, srow_p, m, k,
+                           lam2, (float)srv_step, (float)srv_max);
     });
   });
   if (want_lgrad) return {L_new, rgrad, sqerr, lgrad};

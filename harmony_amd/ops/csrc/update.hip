@@ -18,14 +18,7 @@ __device__ __forceinline__ T apply_one(T v, T d, int mode, float step,
   switch (mode) {
     case ADD: return v + d;
     case ASSIGN: return d;
-    case NMF_SGD: {
-      float x = (float)v - step * (float)d;
-      // compares, not fminf/fmaxf: those return the other operand for a
-      // NaN, and a NaN must stay one as under torch's clamp_
-      x = x < 0.f ? 0.f : x;
-      x = x > maxval ? maxval : x;
-      return (T)x;
-    }
+    case NMF_SGD: return (T)nmf_sgd_one((float)v, (float)d, step, maxval);
     case LDA_COUNTS: {
       T x = v + d;
       return x < (T)0 ? (T)0 : x;
