@@ -9,7 +9,8 @@ server appends (GBTETModelUpdateFunction.java:32). Feature types come from a
 metadata file (GBTMetadataParser.java).
 
 MI355X redesign: exact per-value split scans are replaced by the standard
-GPU-GBT histogram method (K10): features are pre-quantized to NBINS bins
+GPU-GBT histogram method (K10; K10w for levels of more than 8192
+node x bin cells): features are pre-quantized to NBINS bins
 once per data block; each tree level builds (count, sum-residual) histograms
 for ALL nodes x features x bins with one scatter-add over the device-resident
 batch, and best splits come from a parallel prefix-scan of the histograms —
@@ -305,8 +306,10 @@ def build_tree(bins: torch.Tensor, resid: torch.Tensor, num_bins: int,
     (count, sum) for all nodes and one split search; split gain = variance
     reduction. The kinds of input differ in these two steps only:
 
-    dense bins, no feature_types: K10 (ops.gbt_hist) and the tensor-op
-    threshold search (_threshold_search);
+    dense bins, no feature_types: K10 (ops.gbt_hist; K10w behind the same
+    call from the level on at which 2^level * num_bins passes 8192, so deep
+    trees keep their histograms in HIP) and the tensor-op threshold search
+    (_threshold_search);
     dense bins with feature_types (even all zeros): K10 and
     ops.gbt_best_split (K10b), which also searches category subsets;
     SparseBins: K10s and K10b over the batch's present features, the winner

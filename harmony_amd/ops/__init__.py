@@ -21,6 +21,8 @@ Kernel inventory (reference hot loops):
   K7e lda_foldin          held-out document completion (TestDataProvider)
   K9  scatter-apply       LDAETModelUpdateFunction.java:43-64
   K10 gbt_hist            GBTTrainer.java:244+ (histogram method)
+  K10w gbt_hist           K10 for levels wider than 8192 cells: rows sorted by
+                          node, passes over node sub-ranges that fit LDS
   K10b gbt_best_split     GBTTrainer.java bestSplitRealFeature/LabelFeature
   K10s gbt_hist_sparse    K10 over SparseVector samples (GBTETDataParser)
   K10p gbt_forest_predict GBTTrainer.java predictByTree over the whole forest
@@ -1113,13 +1115,23 @@ _APPLY_MODES = {"add": 0, "assign": 1, "nmf_sgd": 2, "lda_counts": 3}
 def gbt_hist(bins: torch.Tensor, resid: torch.Tensor, node: torch.Tensor,
              n_nodes: int, num_bins: int
              ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """GBT level histogram (K10): per-(node, feature, bin) sample counts and
-    residual sums for one tree level. Reference GBTTrainer.java:244+ scans
-    sorted raw values per node/feature on the CPU; the GPU histogram method
-    (pre-quantized bins) is the standard redesign. Returns (cnt, sum),
-    each float32 [n_nodes, F, num_bins]."""
+    """GBT level histogram (K10, K10w): per-(node, feature, bin) sample
+    counts and residual sums for one tree level. Reference
+    GBTTrainer.java:244+ scans sorted raw values per node/feature on the CPU;
+    the GPU histogram method (pre-quantized bins) is the standard redesign.
+    Returns (cnt, sum), each float32 [n_nodes, F, num_bins].
+
+    On the GPU one binding serves every level with num_bins <= 8192: K10
+    (ops/csrc/gbt.hip) holds all nodes of a level of up to
+    n_nodes * num_bins = 8192 cells in LDS; wider levels (the ninth on with
+    64 bins, the seventh on with 256) go to K10w
+    (ops/csrc/gbt_hist_wide.hip), which sorts the rows by node and walks
+    slices of GBT_HIST_WIDE_SLICE sorted rows in passes over node sub-ranges
+    that fit. Counts are exact; a sum is a float32 sum in an order the
+    atomics decide. CPU tensors, HARMONY_FORCE_TORCH_OPS=1 and
+    num_bins > 8192 take the scatter_add_ pair below."""
     B, F = bins.shape
-    if _use_hip(bins) and n_nodes * num_bins <= 8192:
+    if _use_hip(bins) and num_bins <= GBT_HIST_MAX_CELLS:
         cnt = torch.zeros(n_nodes, F, num_bins, device=bins.device)
         s = torch.zeros_like(cnt)
         _hip.gbt_hist(bins.int().contiguous(), resid.float().contiguous(),
@@ -1138,6 +1150,7 @@ def gbt_hist(bins: torch.Tensor, resid: torch.Tensor, node: torch.Tensor,
 
 
 GBT_HIST_MAX_CELLS = 8192    # K10 / K10s: n_nodes * nb cells per feature in LDS
+GBT_HIST_WIDE_SLICE = 1024   # K10w: sorted rows per workgroup
 
 
 def gbt_hist_sparse(feat_ptr: torch.Tensor, feat_row: torch.Tensor,

@@ -6,8 +6,9 @@
 // (sample-tile, feature-chunk) and accumulates (count, residual-sum)
 // histograms for ALL of the level's nodes in LDS with fp32 LDS atomics,
 // then merges once into the global [n_nodes, F, num_bins] arrays. The
-// feature chunk is sized so the per-WG LDS stays <= 64 KB, so any tree
-// depth works (deeper levels -> narrower chunks, more grid.y).
+// feature chunk is sized so the per-WG LDS stays <= 64 KB (deeper levels ->
+// narrower chunks, more grid.y), down to one feature at n_nodes * nb = 8192;
+// wider levels go to K10w (gbt_hist_wide.hip), which groups the rows by node.
 //
 // Why LDS privatization: the torch path's scatter_add issues B*F global
 // atomics into HBM; here each WG's collisions resolve in LDS (~100x the
@@ -64,6 +65,12 @@ __global__ void gbt_hist_kernel(
 
 }  // namespace
 
+// K10w (gbt_hist_wide.hip): the same histogram for n_nodes * nb > 8192.
+void gbt_hist_wide_launch(const char* op, const torch::Tensor& bins,
+                          const torch::Tensor& resid,
+                          const torch::Tensor& node, torch::Tensor& cnt,
+                          torch::Tensor& sum);
+
 void gbt_hist(torch::Tensor bins, torch::Tensor resid, torch::Tensor node,
               torch::Tensor cnt, torch::Tensor sum) {
   check_tensor(__func__, bins, "bins", torch::kInt32, {-1, -1});
@@ -76,10 +83,16 @@ void gbt_hist(torch::Tensor bins, torch::Tensor resid, torch::Tensor node,
   check_below_2_31(__func__, {{"B", bins.size(0)}, {"F", bins.size(1)}});
   TORCH_CHECK(n_nodes >= 1 && nb >= 1, __func__,
               ": cnt needs n_nodes, nb >= 1");
-  TORCH_CHECK((long)n_nodes * nb <= LDS_ENTRIES, __func__,
-              ": level too wide for LDS histogram (use torch fallback)");
+  TORCH_CHECK(nb <= LDS_ENTRIES, __func__, ": more than ", LDS_ENTRIES,
+              " bins, a node too wide for LDS (use torch fallback)");
+  check_below_2_31(__func__, {{"n_nodes", cnt.size(0)}});
   check_on_device(__func__, {bins, resid, node, cnt, sum});
   if (B == 0 || F == 0) return;
+  if ((long)n_nodes * nb > LDS_ENTRIES) {
+    // the level's nodes do not fit one workgroup's LDS together: K10w
+    gbt_hist_wide_launch(__func__, bins, resid, node, cnt, sum);
+    return;
+  }
   const int fc = std::min((long)F, (long)(LDS_ENTRIES / (n_nodes * nb)));
   const int n_chunks = (F + fc - 1) / fc;
   // enough sample tiles to fill the chip once chunks are counted in
